@@ -33,7 +33,16 @@ blocks); the default is weak scaling as described above.
 Warm-up is exactly W steps: nothing else runs the hot path before the timed region (round 2 ran 25 extra "settle"
 steps first; `--settle` still exists for experiments, defaults to 0, and is reported in the line when used).
 
-Besides the contract fields the JSON line carries
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the result line (the contract
+fields, `config`, `stage_ms` and the `roofline` of the timed kernel, all from those K steps and the committed PMC records).
+`--full` adds every side measurement listed below (`pcie_inclusive` / `value_pcie_inclusive`, `arith_fma`, `paths_8f_row1`,
+`roofline_secondary`, `cpu_baseline`, `oht_pair`; for N > 1 `multi_gpu_check`, the non-overlapped steps and the lone
+all-gather); `--no-cpu-baseline` drops the single-GPU ones again (profiler runs).  The synthetic inputs are rendered with
+deterministic reductions, so the same arguments give the same input bits in every run; `--dump-outputs DIR` writes the POI
+records of the last timed step (rank 0: the whole queue) to DIR/pois.npy, float32 -- a queue over 64 MB as a fixed, seeded
+sample of its records, whose row numbers go to DIR/pois_rows.npy.
+
+Besides the contract fields the JSON line of `--full` carries
   value_pcie_inclusive -- SURVEY 8(d)'s own definition of the metric (host POI queue: H2D + D2H of the AoS inside the
                   timed region) as a top-level scalar next to `value` (which the bench contract defines on HBM-resident
                   inputs); details in `pcie_inclusive`,
@@ -119,8 +128,15 @@ def parse():
                          "W steps, as the bench contract says; a non-zero value is reported in the JSON line)")
     ap.add_argument("--size", type=int, default=0, help="override the side of one GPU's image tile (debug; default 4096)")
     ap.add_argument("--pois", type=int, default=0, help="override POIs per GPU side (debug; default 500)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (host-queue rate, the other arithmetic contract, variant paths, secondary "
+                         "rooflines, CPU baselines, the reference's example pair; N > 1: multi_gpu_check and the non-overlapped "
+                         "steps).  Off by default: a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the POI records of the last timed step to DIR/pois.npy (float32; over 64 MB: a fixed, seeded sample "
+                         "of records, row numbers in DIR/pois_rows.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the side measurements (CPU baseline, host-queue rate): profiler runs")
+                    help="with --full: skip the single-GPU side measurements (CPU baseline, host-queue rate, ...): profiler runs")
     ap.add_argument("--cpu-sample", type=int, default=125000)
     ap.add_argument("--arith", choices=["sep", "fma"], default="fma" if os.environ.get("OC_BENCH_ARITH_FMA") == "1" else "sep",
                     help="arithmetic contract of the ICGN kernels in the TIMED region: sep = every multiply and add rounds on its own "
@@ -135,7 +151,39 @@ def parse():
                          "FFTCC windows), 37^3 = 50 653 POIs, FFTCC3D -> ICGN3D1 (conv 1e-3, stop 20), the queue cut into N contiguous "
                          "blocks (strong scaling, as the config is written: 'sharded over 8 x MI355X'), volumes replicated, one all-gather "
                          "of the POI3D records (src/oc_icgn.cpp:1492-1500)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, records):
+    """--dump-outputs: the POI records a caller of the timed path receives from its last step, float32 as they are.  A queue
+    larger than DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of records (sorted row numbers, float64, in pois_rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    records = np.ascontiguousarray(records, dtype=np.float32)
+    rows = None
+    if records.nbytes > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (records.shape[1] * 4 + 8)
+        rows = np.sort(np.random.default_rng(20261016).choice(len(records), k, replace=False))
+        records = records[rows]
+    np.save(os.path.join(path, "pois.npy"), records)
+    if rows is not None:
+        np.save(os.path.join(path, "pois_rows.npy"), rows.astype(np.float64))
+
+
+def render_deterministic(torch, fn, *args, **kwargs):
+    """A synthetic pair rendered on the GPU with deterministic reductions: the renderer sums overlapping speckles with
+    index_add_, whose float atomics would otherwise round a few pixels differently from run to run."""
+    prev = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        return fn(*args, **kwargs)
+    finally:
+        torch.use_deterministic_algorithms(prev)
 
 
 def weak_layout(world, tile=4096, per_side=POIS_PER_GPU_SIDE):
@@ -339,7 +387,7 @@ def main():
         zncc_col, iter_col = 18, 19   # POI3D: result.zncc, result.iteration (src/oc_poi.h:187-222)
         # ONE volume pair for all ranks (rank 0 renders, the others receive it: replicas must be bit-identical to be cross-checked)
         if not dist_on or rank == 0:
-            ref, tar = synth.speckle_pair_3d(dim, dim, dim, seed=20260927, device=dev)
+            ref, tar = render_deterministic(torch, synth.speckle_pair_3d, dim, dim, dim, seed=20260927, device=dev)
         else:
             ref = torch.empty((dim, dim, dim), dtype=torch.float32, device=dev)
             tar = torch.empty((dim, dim, dim), dtype=torch.float32, device=dev)
@@ -369,7 +417,7 @@ def main():
         # atomics, so two renderings of the same seed differ in the last bits of a few pixels -- and with them ~40 of 250 000
         # POIs; ranks working on private renderings could not be cross-checked bit for bit, and would not be "replicas")
         if not dist_on or rank == 0:
-            ref, tar = synth.speckle_pair_2d(height, width, seed=20260925, device=dev)
+            ref, tar = render_deterministic(torch, synth.speckle_pair_2d, height, width, seed=20260925, device=dev)
         else:
             ref = torch.empty((height, width), dtype=torch.float32, device=dev)
             tar = torch.empty((height, width), dtype=torch.float32, device=dev)
@@ -466,10 +514,13 @@ def main():
     fftcc_ms, fftcc_launches = fftcc.profile_read()
     icgn.profile_enable(False)
     fftcc.profile_enable(False)
+    # what the timed path returned in its last step: the whole (gathered) queue, and this rank's block of it
+    full_np = (gathered if dist_on else pois).cpu().numpy()
+    local_np = pois.cpu().numpy()
     # one all-gather on its own, nothing overlapping it (what a caller that needs the field at once would wait for)
     gather_alone_ms = None
     serial_ms = None
-    if dist_on:
+    if dist_on and args.full:
         # the same K steps with the all-gather NOT overlapped: every step waits for its own gather before the next starts
         dist.barrier()
         torch.cuda.synchronize()
@@ -491,16 +542,15 @@ def main():
         gather_alone_ms = (time.perf_counter() - t1) / 3 * 1e3
 
     t = torch.tensor([elapsed, serial_ms or 0.0], dtype=torch.float64, device=dev)
-    full = gathered if dist_on else pois
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t[0].item())
-    serial_ms = float(t[1].item()) if dist_on else None
-    full_np = full.cpu().numpy()
+    serial_ms = float(t[1].item()) if serial_ms is not None else None
     converged = int((full_np[:, zncc_col] >= 0).sum())
-    local_np = pois.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full_np)
     check = multi_gpu_check(args, dist, torch, dev, rank, world, local_rank, one_device, backend, fftcc, icgn, make_pois, n_total,
-                            full_np, local_np, lo, hi, serial_ms) if dist_on else None
+                            full_np, local_np, lo, hi, serial_ms) if (dist_on and args.full) else None
     if is3d:
         if rank == 0:
             print(json.dumps(line_workload_e(args, torch, dev, local_rank, world, dist_on, elapsed, converged, n_total, hi - lo, dim, per_side,
@@ -563,8 +613,8 @@ def main():
             out["settle_steps"] = args.settle
         if check is not None:
             out["multi_gpu_check"] = check
-        # side measurements, skipped with --no-cpu-baseline so that a profiler sees only warm-up + timed steps
-        if world == 1 and not dist_on and not args.no_cpu_baseline:
+        # side measurements: --full only, and skipped with --no-cpu-baseline so that a profiler sees only warm-up + timed steps
+        if args.full and world == 1 and not dist_on and not args.no_cpu_baseline:
             out["pcie_inclusive"] = host_queue_rate(fftcc, icgn, pristine, converged)
             out["value_pcie_inclusive"] = out["pcie_inclusive"]["value"]
             out["arith_fma"] = other_arith_leg(torch, args, fftcc, icgn, queues[0], pristine, icgn_avg_ms, elapsed / args.steps * 1e3)
@@ -631,7 +681,7 @@ def line_workload_e(args, torch, dev, local_rank, world, dist_on, elapsed, conve
     }
     if check is not None:
         out["multi_gpu_check"] = check
-    if world == 1 and not dist_on and not args.no_cpu_baseline:
+    if args.full and world == 1 and not dist_on and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_3d(ref, tar, gx3, gy3, gz3, r, min(args.cpu_sample, 6000))
     return out
 

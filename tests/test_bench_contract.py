@@ -161,3 +161,42 @@ def test_weak_layout_keeps_the_poi_pitch_at_every_n():
     assert bench.weak_layout(2, 512, 40) == (512, 1024, 80, 40)
     with pytest.raises(SystemExit):
         bench.weak_layout(17)
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """`--full` (off by default) gates every side measurement; `--steps` sets the timed steps and must be >= 1."""
+    import bench
+    import sys
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "out"
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert src.count("if args.full and world == 1 and not dist_on and not args.no_cpu_baseline:") == 2
+    assert "if (dist_on and args.full) else None" in src and "if dist_on and args.full:" in src
+
+
+def test_dump_outputs_writes_float32_records_and_samples_large_queues(tmp_path, monkeypatch):
+    import bench
+    rec = np.random.default_rng(1).random((1000, 25)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), rec)
+    got = np.load(tmp_path / "a" / "pois.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rec) and not (tmp_path / "a" / "pois_rows.npy").exists()
+    # over the limit: a fixed, seeded sample of whole records plus their row numbers, the pair within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), rec)
+    got = np.load(tmp_path / "b" / "pois.npy")
+    rows = np.load(tmp_path / "b" / "pois_rows.npy")
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and len(rows) == 20000 // (25 * 4 + 8)
+    assert np.array_equal(got, rec[rows.astype(np.int64)]) and got.nbytes + rows.nbytes <= 20000
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "pois_rows.npy"))

@@ -265,7 +265,7 @@ def test_bench_nccl_backend_at_world_size_one():
     env = dict(os.environ, OC_BENCH_FORCE_DIST="1", OC_BENCH_STRICT="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--size", "1024", "--pois", "64", "--no-cpu-baseline"]
+           "--size", "1024", "--pois", "64", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -297,7 +297,7 @@ def test_bench_control_flow_at_n2_and_n8_on_one_device(nranks):
     tile, per_side = 512, 40
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(nranks), "--steps", "2", "--warmup", "1",
-           "--size", str(tile), "--pois", str(per_side), "--no-cpu-baseline"]
+           "--size", str(tile), "--pois", str(per_side), "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -331,7 +331,7 @@ def test_bench_workload_e_control_flow_at_n2_and_n8_on_one_device(nranks):
     env = dict(os.environ, OC_BENCH_ONE_DEVICE="1", OC_BENCH_STRICT="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(nranks), "--steps", "2", "--warmup", "1",
-           "--workload", "E", "--size", "96", "--pois", "9", "--no-cpu-baseline"]
+           "--workload", "E", "--size", "96", "--pois", "9", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,9 +1,10 @@
 """Drop-in headers vs the reference's own user code (CPU side).
 
-* The reference's example mains compile UNMODIFIED against include/opencorr_compat (needs /root/reference: skipped on the
-  GPU box, where tests/test_gpu_reference_examples.py runs the binaries built from them).
+* The reference's example mains compile UNMODIFIED against include/opencorr_compat (needs the reference tree,
+  oracle.ref.REFERENCE_ROOT: skipped without it; tests/test_gpu_reference_examples.py runs the binaries built from them).
 * Image2D(path) / Image3D(path) decode what the reference's fixtures are (8-bit BMP, `.bin` volumes) plus 24-bit BMP and
   binary PGM, with cv::imread(..., IMREAD_GRAYSCALE)'s grey weights; a file that is not an image fails like a failed imread.
+  The reference's 8-bit fixture oht_cfrp_0.bmp is stored as tests/golden/oht_cfrp_0.bmp.
 """
 import os
 import struct
@@ -12,9 +13,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from oracle.ref import REFERENCE_ROOT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "opencorr_amd", "lib")
-REF = "/root/reference"
+REF = REFERENCE_ROOT
 
 EXAMPLES = ["test_2d_dic_fftcc_icgn1", "test_2d_dic_fftcc_iclm1", "test_2d_dic_fftcc_nr1", "test_2d_dic_strain",
             "test_dvc_fftcc_icgn1", "test_dvc_strain", "test_dvc_gpu_icgn"]
@@ -82,9 +85,7 @@ def test_image2d_decodes_bmp_and_pgm(decoder, tmp_path, golden):
 
 
 def test_image2d_decodes_the_reference_fixture_like_pil(decoder, tmp_path, golden):
-    path = os.path.join(REF, "examples", "2d_dic", "oht_cfrp_0.bmp")
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
+    path = os.path.join(ROOT, "tests", "golden", "oht_cfrp_0.bmp")   # the reference's examples/2d_dic/oht_cfrp_0.bmp
     rc, got = _decode(decoder, "2d", path, tmp_path)
     assert rc == 0 and np.array_equal(got[0], golden["ref"])
 

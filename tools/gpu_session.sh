@@ -4,7 +4,7 @@
 # steps:
 #   test:<pytest args>     python -m pytest <args> -x -q           ("+" stands for a space: test:tests/test_gpu_arith_fma.py, test:-m+gpu)
 #   configs:<A,B,..>       tests/fullsize/run_configs.py --configs ... (both arithmetic modes, oracle samples)  -> configs.json
-#   bench                  the driver's command line                                                              -> bench_n1.json
+#   bench                  bench.py --full with the driver's steps and warm-up (every side measurement)         -> bench_n1.json
 #   benchtrace             rocprofv3 --kernel-trace --stats of the same command                                   -> bench_n1_kernel_stats.csv
 #   profiles:<"B C E">     tools/gpu_profiles.sh (kernel stats + PMC traffic per config)
 #   py:<script and args>   python <script> <args> (underscores for spaces are NOT translated; quote the step)
@@ -22,7 +22,7 @@ for step in "$@"; do
   case $kind in
     test) timeout 1500 python -m pytest ${arg//+/ } -x -q 2>&1 | grep -v amdgpu.ids | tail -15;;
     configs) timeout 2400 python tests/fullsize/run_configs.py --configs $arg --out $OUT/configs_${arg//,/_}.json 2>&1 | grep -v amdgpu | cut -c1-2500;;
-    bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench.err; cut -c1-600 $OUT/bench_n1.json; tail -3 $OUT/bench.err;;
+    bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_n1.json 2> $OUT/bench.err; cut -c1-600 $OUT/bench_n1.json; tail -3 $OUT/bench.err;;
     benchtrace)
       cd /tmp
       timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_n1_under_rocprof.json 2> $OUT/trace.err
