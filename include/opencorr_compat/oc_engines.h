@@ -584,8 +584,8 @@ inline void computeChain(const std::vector<DVC*>& engines, std::vector<POI3D>& p
 
 // Strain(float subregion_radius, int neighbor_number_min, int thread_number)  src/oc_strain.h:34-73.
 // prepare(poi_queue) builds the neighbour search over the queue's coordinates, compute(poi_queue) writes
-// poi.strain of every POI that can be fitted (src/oc_strain.cpp:96-147, 236-247, 476-488).  The POI2DS (stereo)
-// overloads are not offered.
+// poi.strain of every POI that can be fitted (src/oc_strain.cpp:96-147, 236-247, 357-370, 476-488), for POI2D, POI2DS
+// (stereo) and POI3D queues.
 class Strain {
 public:
     Strain(float subregion_radius_, int neighbor_number_min_, int thread_number_)
@@ -607,12 +607,16 @@ public:
 
     void prepare(std::vector<POI2D>& q) { hipdetail::check(oc_hip_strain_prepare(engine_, q.data(), q.size(), sizeof(POI2D), 2, OC_HIP_HOST)); }
     void prepare(std::vector<POI3D>& q) { hipdetail::check(oc_hip_strain_prepare(engine_, q.data(), q.size(), sizeof(POI3D), 3, OC_HIP_HOST)); }
+    // stereo records (src/oc_strain.cpp:111-133, 357-370): neighbours over (x, y), the fit over ref_coor with u, v, w
+    void prepare(std::vector<POI2DS>& q) { hipdetail::check(oc_hip_strain_prepare(engine_, q.data(), q.size(), sizeof(POI2DS), OC_HIP_POI2DS, OC_HIP_HOST)); }
+    void compute(std::vector<POI2DS>& q) { hipdetail::check(oc_hip_strain_compute(engine_, q.data(), q.size(), sizeof(POI2DS), OC_HIP_POI2DS, OC_HIP_HOST)); }
     void compute(std::vector<POI2D>& q) { hipdetail::check(oc_hip_strain_compute(engine_, q.data(), q.size(), sizeof(POI2D), 2, OC_HIP_HOST)); }
     void compute(std::vector<POI3D>& q) { hipdetail::check(oc_hip_strain_compute(engine_, q.data(), q.size(), sizeof(POI3D), 3, OC_HIP_HOST)); }
     // compute(POI*, poi_queue) (src/oc_strain.cpp:149, :372): `poi` must be an element of poi_queue; the whole queue is
     // evaluated on a copy and only that POI's strain is taken over (use the queue overload for more than a few POIs)
     void compute(POI2D* poi, std::vector<POI2D>& q) { one(poi, q, 2); }
     void compute(POI3D* poi, std::vector<POI3D>& q) { one(poi, q, 3); }
+    void compute(POI2DS* poi, std::vector<POI2DS>& q) { one(poi, q, OC_HIP_POI2DS); }  // src/oc_strain.cpp:250
 
 protected:
     float subregion_radius;

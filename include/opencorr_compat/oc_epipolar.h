@@ -7,8 +7,8 @@
 //     epipolarCandidates(...) for every POI -> one candidate queue + segment starts
 //     ICGN2D1::computeBestOf(candidates, segment_starts, poi_queue)   (oc_engines.h: one launch + one selection kernel)
 // Only plain floats cross this header: the fundamental matrix (row-major, what EpipolarSearch::updateFundementalMatrix
-// builds from the two cameras' calibration, :99-118) comes from the caller's calibration code -- Calibration / Stereovision
-// are outside this library's scope.  Every expression below is the reference's, operand for operand; its Eigen product
+// builds from the two cameras' calibration, :99-118) comes from Stereovision / EpipolarSearch of oc_stereo.h, whose
+// EpipolarSearch::compute(poi_queue) is this helper + computeBestOf.  Every expression below is the reference's, operand for operand; its Eigen product
 // fundamental_matrix * view1_vector is restated as the coefficient-wise sum with ascending inner index, (a0 + a1) + a2.  The
 // candidates equal those of the reference's compiled EpipolarSearch bit for bit where that reference is built against
 // oracle/ref_stubs' stand-in Eigen (tests/test_oracle_vs_ref_epipolar.py) -- which sums the three terms in the same order.  Real

@@ -1,11 +1,13 @@
 // oc_io.h -- the reference's result tables, written and read in its own formats.
 //
 // Host-side only.  IO2D / IO3D keep the reference's names and call shapes (src/oc_io.h:53-142) for the table and
-// point functions an FFTCC -> ICGN -> Strain program uses; calibration files and the stereo (POI2DS) tables are not
-// offered.  Formats (src/oc_io.cpp:249-392, 1004-1089): one header line, then one row per POI in fixed notation with
+// point functions an FFTCC -> ICGN -> Strain program uses, the stereo (POI2DS) table included; calibration files and
+// saveMap2DS are not offered.  Formats (src/oc_io.cpp:249-392, 1004-1089): one header line, then one row per POI in fixed notation with
 // 8 decimals, every field followed by the delimiter (also the last one):
 //   saveTable2D             x,y,u,v,u0,v0,ZNCC,iteration,convergence,feature,exx,eyy,exy,subset_rx,subset_ry,
 //   saveDeformationTable2D  x,y,u,ux,uy,uxx,uxy,uyy,v,vx,vy,vxx,vxy,vyy,subset_rx,subset_ry,
+//   saveTable2DS            x,y,u,v,w,r1r2 ZNCC,r1t1 ZNCC,r1t2 ZNCC,r2_x,r2_y,t1_x,t1_y,t2_x,t2_y,ref_x,ref_y,ref_z,tar_x,tar_y,
+//                           tar_z,exx,eyy,ezz,exy,eyz,ezx,subset_rx,subset_ry,                 (src/oc_io.cpp:506-672)
 //   saveTable3D             x,y,z,u,v,w,u0,v0,w0,ZNCC,iteration,convergence,feature,ux,uy,uz,vx,vy,vz,wx,wy,wz,
 //                           exx,eyy,ezz,exy,eyz,ezx,subset_rx,subset_ry,subset_rz,
 // Loaders accept any prefix of the column list (older files of the reference lack the strain / radius columns) and
@@ -141,6 +143,36 @@ public:
         for (const POI2D& p : q) {
             wr << p.x << p.y;
             for (float d : p.deformation.p) wr << d;
+            wr << p.subset_radius.x << p.subset_radius.y;
+            wr.endrow();
+        }
+    }
+    // The stereo table (src/oc_io.cpp:506-672).  The reference's loader indexes all 28 columns; its own example table
+    // examples/3d_dic/GT4-0273_0_epipolar_sift_r16.csv has 26 (no subset radius, general number format): like the other
+    // loaders this one takes any prefix of the column list and leaves the rest zero.
+    std::vector<POI2DS> loadTable2DS() {
+        std::vector<POI2DS> q;
+        for (const auto& r : iodetail::read_rows(file_path, delimiter)) {
+            if (r.size() < 2) continue;
+            POI2DS poi(r[0], r[1]);
+            float* dst = &poi.deformation.u;  // the record's floats follow each other in the table's column order
+            static_assert(sizeof(POI2DS) == 28 * sizeof(float), "POI2DS: 28 packed floats");
+            for (size_t i = 0; i < 26 && i + 2 < r.size(); i++) dst[i] = r[i + 2];
+            q.push_back(poi);
+        }
+        return q;
+    }
+    void saveTable2DS(std::vector<POI2DS>& q) {
+        iodetail::Writer wr(file_path, delimiter, 8);
+        wr.header({"x", "y", "u", "v", "w", "r1r2 ZNCC", "r1t1 ZNCC", "r1t2 ZNCC", "r2_x", "r2_y", "t1_x", "t1_y", "t2_x", "t2_y",
+                   "ref_x", "ref_y", "ref_z", "tar_x", "tar_y", "tar_z", "exx", "eyy", "ezz", "exy", "eyz", "ezx", "subset_rx",
+                   "subset_ry"});
+        for (const POI2DS& p : q) {
+            wr << p.x << p.y;
+            for (float d : p.deformation.p) wr << d;
+            for (float r : p.result.r) wr << r;
+            wr << p.ref_coor.x << p.ref_coor.y << p.ref_coor.z << p.tar_coor.x << p.tar_coor.y << p.tar_coor.z;
+            for (float e : p.strain.e) wr << e;
             wr << p.subset_radius.x << p.subset_radius.y;
             wr.endrow();
         }

@@ -1,8 +1,8 @@
 // oc_types.h -- Eigen/OpenCV-free boundary types with OpenCorr's names and memory layout.
 //
 // These are the PODs that cross the drop-in boundary: Point2D/3D
-// (src/oc_point.h), the POI unions and POI2D/POI3D (src/oc_poi.h:25-222; POI2D = 25 floats,
-// POI3D = 31 floats, no vptr), Image2D with a column-major eg_mat(r, c) accessor like
+// (src/oc_point.h), the POI unions and POI2D/POI2DS/POI3D (src/oc_poi.h:25-222; POI2D = 25 floats,
+// POI2DS = 28 floats, POI3D = 31 floats, no vptr), Image2D with a column-major eg_mat(r, c) accessor like
 // Eigen::MatrixXf (src/oc_image.h:27-45) and Image3D with one contiguous z,y,x block behind
 // vol_mat[z][y][x] (src/oc_image.h:47-68, src/oc_array.h:57-74).  The reference decodes image files with
 // OpenCV (cv::imread(path, IMREAD_GRAYSCALE), src/oc_image.cpp:37-58); here Image2D(path) reads the formats
@@ -59,9 +59,17 @@ union Result2D {
     struct { float u0, v0, zncc, iteration, convergence, feature; };
     float r[6];
 };
+union Result2DS {
+    struct { float r1r2_zncc, r1t1_zncc, r1t2_zncc, r2_x, r2_y, t1_x, t1_y, t2_x, t2_y; };
+    float r[9];
+};
 union DeformationVector3D {
     struct { float u, ux, uy, uz, v, vx, vy, vz, w, wx, wy, wz; };
     float p[12];
+};
+union DisplacementVector3D {
+    struct { float u, v, w; };
+    float p[3];
 };
 union StrainVector3D {
     struct { float exx, eyy, ezz, exy, eyz, ezx; };
@@ -89,6 +97,27 @@ public:
     }
 };
 
+// 3D/stereo DIC, src/oc_poi.h:140-183
+class POI2DS : public Point2D {
+public:
+    DisplacementVector3D deformation;
+    Result2DS result;
+    Point3D ref_coor, tar_coor;
+    StrainVector3D strain;
+    Point2D subset_radius;
+    POI2DS(int x_, int y_) : Point2D(x_, y_) { clear(); }
+    POI2DS(float x_, float y_) : Point2D(x_, y_) { clear(); }
+    POI2DS(Point2D location) : Point2D(location) { clear(); }
+    void clear() {  // everything except the location
+        for (float& v : deformation.p) v = 0.f;
+        for (float& v : result.r) v = 0.f;
+        for (float& v : strain.e) v = 0.f;
+        ref_coor = Point3D();
+        tar_coor = Point3D();
+        subset_radius = Point2D();
+    }
+};
+
 class POI3D : public Point3D {
 public:
     DeformationVector3D deformation;
@@ -107,6 +136,7 @@ public:
 };
 
 static_assert(sizeof(POI2D) == 100, "POI2D must be 25 packed floats (src/oc_poi.h:102-136)");
+static_assert(sizeof(POI2DS) == 112, "POI2DS must be 28 packed floats (src/oc_poi.h:140-183)");
 static_assert(sizeof(POI3D) == 124, "POI3D must be 31 packed floats (src/oc_poi.h:187-222)");
 
 // Column-major float matrix with the slice of Eigen::MatrixXf's interface the hot path's

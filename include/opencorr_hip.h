@@ -73,11 +73,27 @@ typedef enum oc_hip_kind {
     OC_HIP_ICLM2D1 = 7,
     OC_HIP_ICLM2D2 = 8,
     OC_HIP_STRAIN = 9,
-    OC_HIP_REGION_FIT = 10
+    OC_HIP_REGION_FIT = 10,
+    OC_HIP_CALIBRATION = 11,
+    OC_HIP_STEREOVISION = 12
 } oc_hip_kind;
 
 #define OC_HIP_POI2D_BYTES 100
 #define OC_HIP_POI3D_BYTES 124
+/* POI2DS, the stereo record: 28 floats (src/oc_poi.h:53-60, 73-90, 140-183): x, y | u, v, w | r1r2_zncc, r1t1_zncc,
+ * r1t2_zncc, r2_x, r2_y, t1_x, t1_y, t2_x, t2_y | ref_coor x, y, z | tar_coor x, y, z | exx, eyy, ezz, exy, eyz, ezx |
+ * subset_radius x, y */
+#define OC_HIP_POI2DS_BYTES 112
+/* value of `ndim` that selects POI2DS records in oc_hip_strain_prepare / oc_hip_strain_compute (2 = POI2D, 3 = POI3D) */
+#define OC_HIP_POI2DS 22
+
+/* `what` of oc_hip_calibration_get */
+typedef enum oc_hip_calibration_matrix {
+    OC_HIP_CAL_INTRINSIC = 0,   /* 3 x 3 */
+    OC_HIP_CAL_ROTATION = 1,    /* 3 x 3 */
+    OC_HIP_CAL_TRANSLATION = 2, /* 3 */
+    OC_HIP_CAL_PROJECTION = 3   /* 3 x 4 */
+} oc_hip_calibration_matrix;
 
 typedef struct oc_hip_engine oc_hip_engine; /* opaque */
 
@@ -125,11 +141,15 @@ int oc_hip_strain_set(oc_hip_engine* engine, float subregion_radius, int neighbo
                       int approximation);
 /* Strain::prepare(std::vector<POI2D>&) / (std::vector<POI3D>&)  src/oc_strain.cpp:96-107, 136-147: builds the
  * neighbour search over the queue's coordinates (the reference: one kd-tree per thread; here a cell-sorted order on
- * the device).  ndim 2 = POI2D records, 3 = POI3D records; layout and `memory` as for oc_hip_compute. */
+ * the device).  ndim 2 = POI2D records, 3 = POI3D records, OC_HIP_POI2DS = POI2DS records (Strain::prepare(std::vector<POI2DS>&)
+ * :111-133: the search runs over the image coordinates x, y); layout and `memory` as for oc_hip_compute. */
 int oc_hip_strain_prepare(oc_hip_engine* engine, const void* pois, size_t count, size_t stride_bytes, int ndim, int memory);
 /* Strain::compute(std::vector<POI2D>&) src/oc_strain.cpp:236-247 / (std::vector<POI3D>&) :476-488.  Writes
  * strain.exx, eyy, exy (POI2D floats 20..22) or exx, eyy, ezz, exy, eyz, ezx (POI3D floats 22..27) of every POI with
  * ZNCC >= threshold that finds at least neighbor_number_min accepted neighbours; everything else is left untouched.
+ * OC_HIP_POI2DS: Strain::compute(std::vector<POI2DS>&) :357-370 (-> :250-355): a POI takes part, as itself and as a
+ * neighbour, when r1r2_zncc, r1t1_zncc and r1t2_zncc all reach the threshold; the fit runs over ref_coor differences with
+ * u, v, w as right-hand sides and writes the six strains (floats 20..25).
  * The queue must be the one prepare() saw (same length and coordinates). */
 int oc_hip_strain_compute(oc_hip_engine* engine, void* pois, size_t count, size_t stride_bytes, int ndim, int memory);
 /* RegionFit2D / RegionFit3D(float neighbor_search_radius, int neighbor_number_min, int thread_number)
@@ -158,6 +178,51 @@ int oc_hip_region_fit_compute(oc_hip_engine* engine, void* pois, size_t count, s
  * engine handle supplies the device and stream. */
 int oc_hip_select_best(oc_hip_engine* engine, const void* candidates, size_t n_candidates, size_t candidate_stride_bytes,
                        const unsigned* segment_starts, size_t n_segments, void* pois, size_t stride_bytes, int memory);
+/* ---- stereo DIC: Calibration, Stereovision --------------------------------------------------------------------
+ * Handles of these two kinds are created by host arithmetic alone (no device is touched until prepare / maps / undistort /
+ * reconstruct), support set_stream, reset_stream, synchronize, get_kind and destroy like the others, and hold no images.
+ *
+ * Calibration(CameraIntrinsics&, CameraExtrinsics&)  src/oc_calibration.cpp:27-32 -> updateCalibration :87-93 ->
+ * updateMatrices :79-85.  intrinsics = cam_i (fx, fy, fs, cx, cy, k1 ... k6, p1, p2), extrinsics = cam_e (tx, ty, tz, rx, ry,
+ * rz), src/oc_calibration.h:25-45.  The four matrices are float32 host code: updateIntrinsicMatrix :36-48 (an intrinsic
+ * matrix equal to the identity -- "Null intrinsics matrix", :44-47 -- fails with OC_HIP_ERR_INVALID), updateRotationMatrix
+ * :50-60 (Eigen's AngleAxisf::toRotationMatrix for angle |r| about r / |r|; the zero vector gives the exact identity,
+ * handled explicitly), updateTranslationVector :62-67, updateProjectionMatrix :69-77 (K * [R | t], inner index ascending). */
+int oc_hip_calibration_create(const float intrinsics[13], const float extrinsics[6], int device, oc_hip_engine** out);
+/* Calibration::setUndistortion(float convergence, int iteration)  src/oc_calibration.cpp:111-115; defaults 0.001, 40 (:21-25) */
+int oc_hip_calibration_set_undistortion(oc_hip_engine* engine, float convergence, int iteration);
+/* Calibration::prepare(int height, int width)  src/oc_calibration.cpp:161-219: the map of undistorted image coordinates
+ * of every pixel, one thread per pixel, kept on the device.  Completes before it returns.  height, width >= 2. */
+int oc_hip_calibration_prepare(oc_hip_engine* engine, int height, int width);
+/* intrinsic_matrix (9), rotation_matrix (9), translation_vector (3), projection_matrix (12) of
+ * src/oc_calibration.h:53-56, row-major; `what` is an oc_hip_calibration_matrix */
+int oc_hip_calibration_get(const oc_hip_engine* engine, int what, float* out);
+/* map_x / map_y of src/oc_calibration.h:62-63 after prepare, height * width floats each, row-major, copied to the caller's
+ * buffers (`memory` says where they live; either pointer may be null) */
+int oc_hip_calibration_maps(oc_hip_engine* engine, float* map_x, float* map_y, int memory);
+/* Calibration::undistort(Point2D&)  src/oc_calibration.cpp:221-264 for `count` points: (x, y) pairs `stride_bytes` apart in
+ * `in` -> undistorted sensor coordinates at the same positions of `out` (which may be `in`).  The input is not clamped
+ * in place (the reference clamps its argument); a NaN coordinate gives a NaN pair. */
+int oc_hip_calibration_undistort(oc_hip_engine* engine, const void* in, void* out, size_t count, size_t stride_bytes, int memory);
+/* Stereovision(Calibration* view1_cam, Calibration* view2_cam, int thread_number)  src/oc_stereovision.cpp:21-26 +
+ * prepare() :56-68.  Both cameras must outlive the handle (the reference keeps the pointers too) and name the same
+ * device, which becomes the handle's. */
+int oc_hip_stereo_create(oc_hip_engine* view1_cam, oc_hip_engine* view2_cam, oc_hip_engine** out);
+/* Stereovision::updateFundementalMatrix()  src/oc_stereovision.cpp:36-54, row-major 3 x 3, recomputed from the cameras'
+ * present matrices at every call: the 3 x 3 inverses as cofactors over the determinant, the products with ascending inner
+ * index, left to right */
+int oc_hip_stereo_fundamental(oc_hip_engine* engine, float out[9]);
+/* Stereovision::reconstruct(std::vector<Point2D>&, std::vector<Point2D>&, std::vector<Point3D>&)
+ * src/oc_stereovision.cpp:126-133 (-> :70-124): (x, y) pairs of view 1 and view 2, (x, y, z) out, each queue with its own
+ * stride in bytes.  A NaN among the four inputs gives (0, 0, 0).  The 4 x 3 system is built in float32 as written and solved
+ * in double, rounded once (the reference: Eigen's float32 colPivHouseholderQr).  Both cameras must be prepared. */
+int oc_hip_stereo_reconstruct(oc_hip_engine* engine, const void* view1_points, size_t stride1_bytes, const void* view2_points,
+                              size_t stride2_bytes, void* points3d, size_t stride_out_bytes, size_t count, int memory);
+/* The host loops of examples/test_3d_dic_epipolar_sift.cpp:303-317 as one launch over a POI2DS queue: ref_coor =
+ * reconstruct((x, y), (r2_x, r2_y)), tar_coor = reconstruct((t1_x, t1_y), (t2_x, t2_y)), deformation = tar_coor - ref_coor;
+ * nothing else of a record is written. */
+int oc_hip_stereo_reconstruct_pois(oc_hip_engine* engine, void* pois2ds, size_t count, size_t stride_bytes, int memory);
+
 /* The two selections of the RegionFit -> re-ICGN loop (examples/test_3d_reconstruction_sift_icgn2_regfit.cpp:214-260), as
  * order-preserving partitions ON THE DEVICE, so that a queue resident in HBM never travels to the host between ICGN,
  * RegionFit and the next ICGN pass.  Any engine handle supplies the device and the stream; ndim = 2 (POI2D) / 3 (POI3D);

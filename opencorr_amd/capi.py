@@ -18,8 +18,11 @@ ERR_INVALID, ERR_HIP, ERR_ROCFFT, ERR_NOMEM, ERR_UNSUPPORTED = 1, 2, 3, 4, 5
 HOST, DEVICE = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 FFTCC2D, ICGN2D1, ICGN2D2, FFTCC3D, ICGN3D1, NR2D1, ICLM2D1, ICLM2D2, STRAIN, REGION_FIT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
-POI2D_BYTES, POI3D_BYTES = 100, 124
-POI2D_FLOATS, POI3D_FLOATS = 25, 31
+CALIBRATION, STEREOVISION = 11, 12
+POI2D_BYTES, POI3D_BYTES, POI2DS_BYTES = 100, 124, 112
+POI2D_FLOATS, POI3D_FLOATS, POI2DS_FLOATS = 25, 31, 28
+POI2DS = 22  # the `ndim` of oc_hip_strain_prepare / oc_hip_strain_compute that selects POI2DS records
+CAL_INTRINSIC, CAL_ROTATION, CAL_TRANSLATION, CAL_PROJECTION = 0, 1, 2, 3
 
 # every symbol include/opencorr_hip.h declares (tests check the .so exports them all)
 SYMBOLS = [
@@ -37,6 +40,9 @@ SYMBOLS = [
     "oc_hip_get_kind", "oc_hip_get_field", "oc_hip_read_field",
     "oc_hip_profile_enable", "oc_hip_profile_read", "oc_hip_profile_reset",
     "oc_hip_set_devices", "oc_hip_get_devices", "oc_hip_group_queue",
+    "oc_hip_calibration_create", "oc_hip_calibration_set_undistortion", "oc_hip_calibration_prepare", "oc_hip_calibration_get",
+    "oc_hip_calibration_maps", "oc_hip_calibration_undistort",
+    "oc_hip_stereo_create", "oc_hip_stereo_fundamental", "oc_hip_stereo_reconstruct", "oc_hip_stereo_reconstruct_pois",
 ]
 
 
@@ -166,6 +172,16 @@ def lib():
     L.oc_hip_set_devices.argtypes = [vp, ctypes.POINTER(i), i]
     L.oc_hip_get_devices.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(i)]
     L.oc_hip_group_queue.argtypes = [vp, i, pp, ctypes.POINTER(sz)]
+    L.oc_hip_calibration_create.argtypes = [vp, vp, i, pp]
+    L.oc_hip_calibration_set_undistortion.argtypes = [vp, f, i]
+    L.oc_hip_calibration_prepare.argtypes = [vp, i, i]
+    L.oc_hip_calibration_get.argtypes = [vp, i, vp]
+    L.oc_hip_calibration_maps.argtypes = [vp, vp, vp, i]
+    L.oc_hip_calibration_undistort.argtypes = [vp, vp, vp, sz, sz, i]
+    L.oc_hip_stereo_create.argtypes = [vp, vp, pp]
+    L.oc_hip_stereo_fundamental.argtypes = [vp, vp]
+    L.oc_hip_stereo_reconstruct.argtypes = [vp, vp, sz, vp, sz, vp, sz, sz, i]
+    L.oc_hip_stereo_reconstruct_pois.argtypes = [vp, vp, sz, sz, i]
     for name in SYMBOLS:
         if name != "oc_hip_last_error":
             getattr(L, name).restype = i

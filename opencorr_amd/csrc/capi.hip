@@ -806,6 +806,8 @@ int oc_hip_set_devices(oc_hip_engine* e, const int* device_ids, int n_devices) {
     DeviceScope device_scope;
     if (e->is_replica) return fail(OC_HIP_ERR_INVALID, "set_devices: this handle is a group member");
     if (!device_ids || n_devices < 1) return fail(OC_HIP_ERR_INVALID, "set_devices: need at least one device id");
+    if (e->kind == OC_HIP_CALIBRATION || e->kind == OC_HIP_STEREOVISION)
+        return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Calibration / Stereovision handles stay on the device they were created for");
     if (n_devices > 1 && (e->kind == OC_HIP_STRAIN || e->kind == OC_HIP_REGION_FIT))
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Strain / RegionFit need every neighbour of a POI and stay on one device");
     int ndev = 0;

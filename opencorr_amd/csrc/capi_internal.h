@@ -193,6 +193,17 @@ struct oc_hip_engine {
     size_t st_count = 0;  // queue length the grid was prepared for (0 = not prepared)
     ochip::StrainGrid st_grid{};
     DevBuf st_box, st_counts, st_start, st_cursor, st_slots, st_order, st_recs, st_fallback;
+    // Calibration (src/oc_calibration.h:47-97): the 13 + 6 numbers, the four small matrices (host code, row-major), the
+    // undistortion map on the device.  Stereovision (src/oc_stereovision.h): the two cameras (handles the caller keeps alive,
+    // like the reference's Calibration pointers) and the fundamental matrix.  Handles of these two kinds are created without
+    // touching the device (the matrices are host arithmetic); the stream is made by the first call that needs the GPU.
+    float cal_i[13] = {}, cal_e[6] = {};
+    float cal_K[9] = {}, cal_R[9] = {}, cal_T[3] = {}, cal_P[12] = {};
+    float cal_conv = 0.001f;
+    int cal_iter = 40, cal_h = 0, cal_w = 0;
+    DevBuf cal_map_x, cal_map_y, cal_stage;
+    oc_hip_engine* stereo_cam[2] = {nullptr, nullptr};
+    float stereo_F[9] = {};
     float lm_lambda = 100.f, lm_alpha = 0.1f, lm_beta = 10.f;  // DampingParameter defaults, src/oc_iclm.h:33-38
     int icgn2d_tile_px = 128;  // 0 = visit the queue in its own order (64 until round 3; 128 suits the lockstep sweeps: 3.29 vs 3.34 ms)
     // FFTCC working set
@@ -286,9 +297,13 @@ inline int check_engine(const oc_hip_engine* e) {
     return OC_HIP_OK;
 }
 
+int make_own_stream(oc_hip_engine* e);  // capi_stereo.hip
+
 inline int activate(const oc_hip_engine* e) {
     OC_TRY(check_engine(e));
     OC_HIP_TRY(hipSetDevice(e->device));
+    // Calibration / Stereovision handles are created on the host alone: their stream comes with the first device call
+    if (!e->own_stream) OC_TRY(make_own_stream(const_cast<oc_hip_engine*>(e)));
     return OC_HIP_OK;
 }
 

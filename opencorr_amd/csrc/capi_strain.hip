@@ -61,12 +61,21 @@ int oc_hip_strain_set(oc_hip_engine* e, float subregion_radius, int neighbor_num
     return OC_HIP_OK;
 }
 
+// record bytes of an `ndim` value; the neighbour search of POI2DS records runs over (x, y): the 2D grid
+static size_t strain_record_bytes(int ndim) {
+    return ndim == 2 ? OC_HIP_POI2D_BYTES : ndim == 3 ? OC_HIP_POI3D_BYTES : OC_HIP_POI2DS_BYTES;
+}
+static int strain_search_dim(int ndim) { return ndim == OC_HIP_POI2DS ? 2 : ndim; }
+
 static int strain_stage(oc_hip_engine* e, const void* pois, size_t count, size_t stride_bytes, int ndim, int memory,
                         float** d_pois) {
     if (e->kind != OC_HIP_STRAIN && e->kind != OC_HIP_REGION_FIT) return fail(OC_HIP_ERR_INVALID, "not a Strain / RegionFit engine");
-    if (ndim != 2 && ndim != 3) return fail(OC_HIP_ERR_INVALID, "ndim must be 2 (POI2D) or 3 (POI3D), got %d", ndim);
+    if (ndim == OC_HIP_POI2DS && e->kind != OC_HIP_STRAIN)
+        return fail(OC_HIP_ERR_INVALID, "ndim must be 2 (POI2D) or 3 (POI3D), got %d (POI2DS records are Strain's alone)", ndim);
+    if (ndim != 2 && ndim != 3 && ndim != OC_HIP_POI2DS)
+        return fail(OC_HIP_ERR_INVALID, "ndim must be 2 (POI2D), 3 (POI3D) or OC_HIP_POI2DS (%d), got %d", OC_HIP_POI2DS, ndim);
     if (!pois) return fail(OC_HIP_ERR_INVALID, "null POI buffer");
-    const size_t rec = ndim == 2 ? OC_HIP_POI2D_BYTES : OC_HIP_POI3D_BYTES;
+    const size_t rec = strain_record_bytes(ndim);
     if (stride_bytes < rec || (stride_bytes & 3))
         return fail(OC_HIP_ERR_INVALID, "bad POI stride %zu (record is %zu bytes, stride must be a multiple of 4)", stride_bytes, rec);
     if (count > 0x7fffffffull) return fail(OC_HIP_ERR_UNSUPPORTED, "Strain: at most 2^31-1 POIs per queue");
@@ -95,18 +104,19 @@ static int plane_prepare(oc_hip_engine* e, int kind, const void* pois, size_t co
     const int stride_f = (int)(stride_bytes / 4);
     // bounding box -> grid (the cell count is needed on the host to size the tables)
     OC_TRY(e->st_box.reserve(6 * sizeof(unsigned)));
-    OC_HIP_TRY(ochip::launch_strain_bbox(ndim, d_pois, stride_f, count, e->st_box.as<unsigned>(), e->stream));
+    const int sdim = strain_search_dim(ndim);
+    OC_HIP_TRY(ochip::launch_strain_bbox(sdim, d_pois, stride_f, count, e->st_box.as<unsigned>(), e->stream));
     unsigned box[6];
     OC_HIP_TRY(hipMemcpyAsync(box, e->st_box.p, sizeof(box), hipMemcpyDeviceToHost, e->stream));
     OC_HIP_TRY(hipStreamSynchronize(e->stream));
-    const ochip::StrainGrid g = ochip::strain_make_grid(ndim, box, e->st_radius);
+    const ochip::StrainGrid g = ochip::strain_make_grid(sdim, box, e->st_radius);
     const size_t ncell = ochip::strain_cell_count(g);
     OC_TRY(e->st_counts.reserve(ncell * sizeof(unsigned)));
     OC_TRY(e->st_cursor.reserve(ncell * sizeof(unsigned)));
     OC_TRY(e->st_start.reserve((ncell + 1) * sizeof(unsigned)));
     OC_TRY(e->st_slots.reserve(count * sizeof(unsigned)));
     OC_TRY(e->st_order.reserve(count * sizeof(unsigned)));
-    OC_HIP_TRY(ochip::launch_strain_sort(ndim, d_pois, stride_f, count, g, e->st_counts.as<unsigned>(), e->st_start.as<unsigned>(),
+    OC_HIP_TRY(ochip::launch_strain_sort(sdim, d_pois, stride_f, count, g, e->st_counts.as<unsigned>(), e->st_start.as<unsigned>(),
                                          e->st_cursor.as<unsigned>(), e->st_slots.as<unsigned>(), e->st_order.as<unsigned>(),
                                          e->stream));
     if (gather_records) {
@@ -169,15 +179,19 @@ int oc_hip_strain_compute(oc_hip_engine* e, void* pois, size_t count, size_t str
     if (e->kind != OC_HIP_STRAIN) return fail(OC_HIP_ERR_INVALID, "not a Strain engine");
     if (e->st_count == 0) return fail(OC_HIP_ERR_INVALID, "Strain: prepare(poi_queue) has not been called (or the radius changed since)");
     if (e->st_count != count || e->st_ndim != ndim)
-        return fail(OC_HIP_ERR_INVALID, "Strain: prepare() saw %zu POI%dD, compute() got %zu POI%dD", e->st_count, e->st_ndim, count, ndim);
+        return fail(OC_HIP_ERR_INVALID, "Strain: prepare() saw %zu records of ndim %d, compute() got %zu of ndim %d", e->st_count, e->st_ndim, count, ndim);
     OC_TRY(order_after_default_stream(e));
     float* d_pois = nullptr;
     OC_TRY(strain_stage(e, pois, count, stride_bytes, ndim, memory, &d_pois));
     const int stride_f = (int)(stride_bytes / 4);
-    OC_TRY(e->st_recs.reserve(count * 32));
+    OC_TRY(e->st_recs.reserve(count * (ndim == OC_HIP_POI2DS ? 48 : 32)));
     OC_TRY(e->st_fallback.reserve((count + 1) * sizeof(unsigned)));
     const ochip::StrainParams P = {e->st_radius * e->st_radius, e->st_zncc, e->st_nmin, e->st_approx};
-    {
+    if (ndim == OC_HIP_POI2DS) {
+        ProfScope prof(e);
+        OC_HIP_TRY(ochip::launch_strain2ds_compute(d_pois, stride_f, count, e->st_grid, P, e->st_start.as<unsigned>(),
+                                                   e->st_order.as<unsigned>(), e->st_recs.p, e->st_fallback.as<unsigned>(), e->stream));
+    } else {
         ProfScope prof(e);
         OC_HIP_TRY(ochip::launch_strain_compute(ndim, d_pois, stride_f, count, e->st_grid, P, e->st_start.as<unsigned>(),
                                                 e->st_order.as<unsigned>(), e->st_recs.p, e->st_fallback.as<unsigned>(), e->stream));

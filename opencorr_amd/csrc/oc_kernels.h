@@ -134,6 +134,44 @@ hipError_t launch_strain_compute(int ndim, float* pois, int stride_floats, size_
                                  const StrainParams& P, const unsigned* start, const unsigned* order, void* recs,
                                  unsigned* fallback, hipStream_t stream);
 
+// Strain::compute(std::vector<POI2DS>&) (src/oc_strain.cpp:250-370): the neighbour search is the 2D one over (x, y) --
+// launch_strain_bbox / launch_strain_sort with ndim 2 on the 28-float records -- the fit has four columns over ref_coor.
+// recs: count * 48 bytes
+hipError_t launch_strain2ds_compute(float* pois, int stride_floats, size_t count, const StrainGrid& g, const StrainParams& P,
+                                    const unsigned* start, const unsigned* order, void* recs, unsigned* fallback,
+                                    hipStream_t stream);
+
+// float offsets inside a POI2DS, the stereo record (src/oc_poi.h:53-60, 73-90, 140-183): x, y | u, v, w | r1r2, r1t1, r1t2 zncc,
+// r2, t1, t2 | ref_coor | tar_coor | six strains | subset_radius
+namespace poi2ds {
+constexpr int X = 0, Y = 1, U = 2, V = 3, W = 4, R1R2_ZNCC = 5, R1T1_ZNCC = 6, R1T2_ZNCC = 7, R2_X = 8, R2_Y = 9, T1_X = 10,
+              T1_Y = 11, T2_X = 12, T2_Y = 13, REF = 14, TAR = 17, EXX = 20, SRX = 26, SRY = 27;
+constexpr int FLOATS = 28;
+}  // namespace poi2ds
+
+// ---- stereo.hip -------------------------------------------------------------
+// Calibration::prepare / undistort (src/oc_calibration.cpp:161-264), Stereovision::reconstruct (src/oc_stereovision.cpp:70-133)
+struct CameraParams {
+    float fx, fy, fs, cx, cy, k1, k2, k3, k4, k5, k6, p1, p2;  // CameraIntrinsics::cam_i order, src/oc_calibration.h:25-35
+};
+struct CameraView {
+    CameraParams cam;
+    const float* map_x;  // height * width, row-major
+    const float* map_y;
+    int height, width;
+    float proj[12];  // projection matrix, row-major 3 x 4
+};
+hipError_t launch_undistort_map(const CameraParams& cam, int height, int width, float convergence, int iteration, float* map_x,
+                                float* map_y, hipStream_t stream);
+hipError_t launch_undistort_points(const CameraView& view, const float* in, float* out, int stride_floats, size_t count,
+                                   hipStream_t stream);
+hipError_t launch_reconstruct(const CameraView& view1, const CameraView& view2, const float* p1, int stride1_floats,
+                              const float* p2, int stride2_floats, float* out, int stride_out_floats, size_t count,
+                              hipStream_t stream);
+// every POI2DS record: ref_coor <- (x, y) / (r2), tar_coor <- (t1) / (t2), deformation <- tar_coor - ref_coor
+hipError_t launch_reconstruct_pois(const CameraView& view1, const CameraView& view2, float* pois, int stride_floats, size_t count,
+                                   hipStream_t stream);
+
 // best candidate (highest ZNCC) of every segment of a candidate queue -> deformation + result of the segment's POI
 hipError_t launch_poi2d_best_of_segments(const float* cand, int cand_stride_floats, const unsigned* seg_start, size_t nseg,
                                          float* pois, int stride_floats, hipStream_t stream);

@@ -1,8 +1,9 @@
 // strain.hip -- Strain::prepare + Strain::compute(poi_queue) on gfx950.
 //
-// Replaces Strain::compute(std::vector<POI2D>&) (src/oc_strain.cpp:236-247 -> :149-234) and
-// Strain::compute(std::vector<POI3D>&) (:476-488 -> :372-473) with the neighbour search of Strain::prepare
-// (:96-147, a nanoflann kd-tree per thread in the reference).
+// Replaces Strain::compute(std::vector<POI2D>&) (src/oc_strain.cpp:236-247 -> :149-234),
+// Strain::compute(std::vector<POI3D>&) (:476-488 -> :372-473) and Strain::compute(std::vector<POI2DS>&) (:357-370 ->
+// :250-355, the stereo record: "POI2DS" below) with the neighbour search of Strain::prepare (:96-147, a nanoflann kd-tree
+// per thread in the reference).
 //
 // What the reference fixes and what it leaves to third-party code is stated with the oracle's restatement
 // (oracle/oc_oracle.cpp, "Strain"); this file performs the same operations in the same order and is bit-identical to
@@ -250,13 +251,13 @@ struct Fit {
     }
 };
 
-// strain formulas, src/oc_strain.cpp:220-234 (2D), :446-466 (3D)
-template <int DIM>
+// strain formulas, src/oc_strain.cpp:220-234 (2D), :446-466 (3D), :335-353 (POI2DS: the 3D formulas, E0 = 20)
+template <int DIM, int E0 = Lay<DIM>::E0>
 __device__ __forceinline__ void write_strain(float* __restrict__ poi, Fit<DIM>& fit, int approximation) {
     constexpr int D = DIM + 1;
     double grad[DIM][D];
     fit.solve(grad);
-    float* e = poi + Lay<DIM>::E0;
+    float* e = poi + E0;
     if constexpr (DIM == 2) {
         const float ux = (float)grad[0][1], uy = (float)grad[0][2], vx = (float)grad[1][1], vy = (float)grad[1][2];
         if (approximation == 1) {
@@ -470,6 +471,162 @@ __global__ __launch_bounds__(64) void strain_knn_kernel(float* __restrict__ pois
         write_plane<DIM>(me.poi, fit);
 }
 
+// ---- POI2DS (stereo) ------------------------------------------------------------------------------------------
+// Strain::compute(POI2DS*, queue), src/oc_strain.cpp:250-370: neighbours are searched over the image coordinates (x, y)
+// (:111-133, the 2D cell grid), a neighbour counts when all three ZNCCs reach the threshold (:268-270), the fit has the
+// four columns (1, d ref_coor) with float differences (:310) and the right-hand sides u, v, w.  48-byte records:
+// {x, y, ref.x, ref.y | ref.z, u, v, w | gate, queue index, -, -}; gate = the smallest of the three ZNCCs (NaN when any
+// is NaN), so that `gate >= threshold` is the reference's three-fold test.
+struct alignas(16) Strain2sRec {
+    float x, y, rx, ry;
+    float rz, u, v, w;
+    float gate;
+    unsigned idx;
+    float pad0, pad1;
+};
+
+__global__ __launch_bounds__(256) void strain2s_gather_kernel(const float* __restrict__ pois, int stride_f, unsigned count,
+                                                              const unsigned* __restrict__ order, Strain2sRec* __restrict__ recs) {
+    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const unsigned i = order[k];
+    const float* p = pois + (size_t)i * stride_f;
+    Strain2sRec r;
+    r.x = p[poi2ds::X];
+    r.y = p[poi2ds::Y];
+    r.rx = p[poi2ds::REF];
+    r.ry = p[poi2ds::REF + 1];
+    r.rz = p[poi2ds::REF + 2];
+    r.u = p[poi2ds::U];
+    r.v = p[poi2ds::V];
+    r.w = p[poi2ds::W];
+    const float a = p[poi2ds::R1R2_ZNCC], b = p[poi2ds::R1T1_ZNCC], c = p[poi2ds::R1T2_ZNCC];
+    float gate = a;
+    if (!(b >= gate)) gate = b == b && gate == gate ? b : NAN;
+    if (!(c >= gate)) gate = c == c && gate == gate ? c : NAN;
+    r.gate = gate;
+    r.idx = i;
+    r.pad0 = r.pad1 = 0.f;
+    recs[k] = r;
+}
+
+struct Query2s {
+    float x, y, rx, ry, rz;
+    float* poi;
+};
+
+__device__ __forceinline__ bool load_query2s(Query2s& me, unsigned k, float* __restrict__ pois, int stride_f,
+                                             const float4* __restrict__ rv, const StrainParams& P) {
+    const float4 m0 = rv[3 * (size_t)k], m1 = rv[3 * (size_t)k + 1], m2 = rv[3 * (size_t)k + 2];
+    me.x = m0.x;
+    me.y = m0.y;
+    me.rx = m0.z;
+    me.ry = m0.w;
+    me.rz = m1.x;
+    me.poi = pois + (size_t)__float_as_uint(m2.y) * stride_f;
+    return m2.x >= P.zncc_threshold;  // src/oc_strain.cpp:363-365
+}
+
+__global__ __launch_bounds__(256) void strain2s_fit_kernel(float* __restrict__ pois, int stride_f, unsigned count, StrainGrid g,
+                                                           StrainParams P, const unsigned* __restrict__ start,
+                                                           const Strain2sRec* __restrict__ recs, unsigned* __restrict__ fallback) {
+    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const float4* rv = reinterpret_cast<const float4*>(recs);
+    Query2s me;
+    if (!load_query2s(me, k, pois, stride_f, rv, P)) return;
+    const Query q2 = {me.x, me.y, 0.f, nullptr};
+    const float pos[3] = {me.x, me.y, 0.f};
+    int cx, cy, cz;
+    cell_of<2>(pos, g, cx, cy, cz);
+    Fit<3> fit;
+    fit.clear();
+    int inside = 0;
+    for (int dy = -1; dy <= 1; dy++) {
+        const int y = cy + dy;
+        if (y < 0 || y >= g.ncy) continue;
+        const int xa = max(cx - 1, 0), xb = min(cx + 1, g.ncx - 1);
+        const size_t rowc = (size_t)y * g.ncx;
+        const unsigned s = start[rowc + xa], e = start[rowc + xb + 1];
+        for (unsigned q = s; q < e; q++) {
+            const float4 a = rv[3 * (size_t)q];
+            if (dist2<2>(q2, a.x, a.y, 0.f) < P.radius2) {
+                inside++;
+                const float4 b = rv[3 * (size_t)q + 1];
+                if (rv[3 * (size_t)q + 2].x >= P.zncc_threshold) fit.add(a.z - me.rx, a.w - me.ry, b.x - me.rz, b.y, b.z, b.w);
+            }
+        }
+    }
+    if (inside < P.neighbor_min) {
+        fallback[1 + atomicAdd(fallback, 1u)] = k;  // the KNN path, strain2s_knn_kernel
+        return;
+    }
+    if (fit.n < P.neighbor_min) return;  // src/oc_strain.cpp:297
+    write_strain<3, poi2ds::EXX>(me.poi, fit, P.approximation);
+}
+
+// KNN path (src/oc_strain.cpp:276-293), as strain_knn_kernel<2, 0> with the four-column fit
+__global__ __launch_bounds__(64) void strain2s_knn_kernel(float* __restrict__ pois, int stride_f, StrainGrid g, StrainParams P,
+                                                          const unsigned* __restrict__ start, const Strain2sRec* __restrict__ recs,
+                                                          const unsigned* __restrict__ fallback) {
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= fallback[0]) return;
+    const unsigned k = fallback[1 + t];
+    const float4* rv = reinterpret_cast<const float4*>(recs);
+    Query2s me;
+    load_query2s(me, k, pois, stride_f, rv, P);
+    const Query q2 = {me.x, me.y, 0.f, nullptr};
+    const float pos[3] = {me.x, me.y, 0.f};
+    int cx, cy, cz;
+    cell_of<2>(pos, g, cx, cy, cz);
+    const int K = P.neighbor_min;
+    float bd[kKnnMax];     // ascending (d2, idx)
+    unsigned bi[kKnnMax];  // queue index
+    unsigned bq[kKnnMax];  // record slot
+    int have = 0;
+    const float pitch = 1.f / g.inv_pitch;
+    const int reach = max(g.ncx, g.ncy);
+    for (int ring = 0; ring <= reach; ring++) {
+        for (int dy = -ring; dy <= ring; dy++)
+            for (int dx = -ring; dx <= ring; dx++) {
+                if (max(abs(dx), abs(dy)) != ring) continue;  // the shell only
+                const int x = cx + dx, y = cy + dy;
+                if (x < 0 || y < 0 || x >= g.ncx || y >= g.ncy) continue;
+                const size_t c = (size_t)y * g.ncx + x;
+                for (unsigned q = start[c]; q < start[c + 1]; q++) {
+                    const float4 a = rv[3 * (size_t)q];
+                    const unsigned idx = __float_as_uint(rv[3 * (size_t)q + 2].y);
+                    const float d = dist2<2>(q2, a.x, a.y, 0.f);
+                    if (!(d == d)) continue;  // NaN coordinates never enter
+                    if (have == K && !(d < bd[K - 1] || (d == bd[K - 1] && idx < bi[K - 1]))) continue;
+                    int p = have < K ? have : K - 1;
+                    while (p > 0 && (d < bd[p - 1] || (d == bd[p - 1] && idx < bi[p - 1]))) {
+                        bd[p] = bd[p - 1];
+                        bi[p] = bi[p - 1];
+                        bq[p] = bq[p - 1];
+                        p--;
+                    }
+                    bd[p] = d;
+                    bi[p] = idx;
+                    bq[p] = q;
+                    if (have < K) have++;
+                }
+            }
+        if (have == K) {
+            const float lim = (float)ring * pitch * 0.999f;
+            if (bd[K - 1] < lim * lim) break;
+        }
+    }
+    Fit<3> fit;
+    fit.clear();
+    for (int j = 0; j < have; j++) {
+        const float4 a = rv[3 * (size_t)bq[j]], b = rv[3 * (size_t)bq[j] + 1];
+        if (rv[3 * (size_t)bq[j] + 2].x >= P.zncc_threshold) fit.add(a.z - me.rx, a.w - me.ry, b.x - me.rz, b.y, b.z, b.w);
+    }
+    if (fit.n < K) return;
+    write_strain<3, poi2ds::EXX>(me.poi, fit, P.approximation);
+}
+
 float unord(unsigned u) {
     const unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
     float f;
@@ -598,6 +755,28 @@ hipError_t launch_region_fit_compute(int ndim, float* pois, int stride_f, size_t
     if (count == 0) return hipSuccess;
     return ndim == 2 ? fit_t<2, 1>(pois, stride_f, count, g, P, start, recs, fallback, stream)
                      : fit_t<3, 1>(pois, stride_f, count, g, P, start, recs, fallback, stream);
+}
+
+}  // namespace ochip
+
+namespace ochip {
+
+// Strain::compute(std::vector<POI2DS>&): `pois` is the queue prepare() sorted (ndim 2 over x, y).  recs: count * 48 bytes
+hipError_t launch_strain2ds_compute(float* pois, int stride_f, size_t count, const StrainGrid& g, const StrainParams& P,
+                                    const unsigned* start, const unsigned* order, void* recs, unsigned* fallback,
+                                    hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    hipError_t err = hipMemsetAsync(fallback, 0, sizeof(unsigned), stream);
+    if (err != hipSuccess) return err;
+    const unsigned blocks = (unsigned)((count + 255) / 256);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(strain2s_gather_kernel, dim3(blocks), dim3(256), 0, stream, pois, stride_f, (unsigned)count, order,
+                       static_cast<Strain2sRec*>(recs));
+    hipLaunchKernelGGL(strain2s_fit_kernel, dim3(blocks), dim3(256), 0, stream, pois, stride_f, (unsigned)count, g, P, start,
+                       static_cast<const Strain2sRec*>(recs), fallback);
+    hipLaunchKernelGGL(strain2s_knn_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, pois, stride_f, g, P, start,
+                       static_cast<const Strain2sRec*>(recs), fallback);
+    return hipGetLastError();
 }
 
 }  // namespace ochip

@@ -459,8 +459,9 @@ class Strain:
     """Strain(subregion_radius, neighbor_number_min, thread_number) -- src/oc_strain.h:34-73, src/oc_strain.cpp:31-46.
 
     ``prepare(pois)`` builds the neighbour search over the queue's coordinates, ``compute(pois)`` writes the strain
-    fields of every POI that can be fitted, in place (POI2D: exx, eyy, exy; POI3D: exx, eyy, ezz, exy, eyz, ezx).
-    ``pois`` is a float32 (n, 25) / (n, 31) NumPy array (host path) or CUDA torch tensor (used in place)."""
+    fields of every POI that can be fitted, in place (POI2D: exx, eyy, exy; POI3D and POI2DS: exx, eyy, ezz, exy, eyz,
+    ezx).  ``pois`` is a float32 (n, 25) / (n, 31) / (n, 28) NumPy array (host path) or CUDA torch tensor (used in place);
+    28 floats are the stereo record POI2DS (``P2S``): neighbours over (x, y), the fit over ``ref_coor`` with u, v, w."""
 
     def __init__(self, subregion_radius, neighbor_number_min, thread_number=1, device=0):
         self._h = ctypes.c_void_p()
@@ -518,9 +519,10 @@ class Strain:
                 raise ValueError("pois must be a C-contiguous float32 array of shape (n, 25) or (n, 31)")
             p, mem = ctypes.c_void_p(pois.ctypes.data), capi.HOST
             n, floats, stride = pois.shape[0], pois.shape[1], pois.strides[0]
-        if floats not in (capi.POI2D_FLOATS, capi.POI3D_FLOATS):
-            raise ValueError("POI records have 25 (POI2D) or 31 (POI3D) floats, got %d" % floats)
-        return p, n, stride, (2 if floats == capi.POI2D_FLOATS else 3), mem
+        ndim = {capi.POI2D_FLOATS: 2, capi.POI3D_FLOATS: 3, capi.POI2DS_FLOATS: capi.POI2DS}.get(floats)
+        if ndim is None:
+            raise ValueError("POI records have 25 (POI2D), 31 (POI3D) or 28 (POI2DS) floats, got %d" % floats)
+        return p, n, stride, ndim, mem
 
     def prepare(self, pois):
         self._adopt_stream_of(pois)
@@ -544,6 +546,170 @@ class Strain:
         n = ctypes.c_long()
         capi.check(capi.lib().oc_hip_profile_read(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+# float offsets inside a POI2DS record (src/oc_poi.h:53-60, 73-90, 140-183)
+P2S = dict(x=0, y=1, u=2, v=3, w=4, r1r2_zncc=5, r1t1_zncc=6, r1t2_zncc=7, r2_x=8, r2_y=9, t1_x=10, t1_y=11, t2_x=12, t2_y=13,
+           ref_x=14, ref_y=15, ref_z=16, tar_x=17, tar_y=18, tar_z=19, exx=20, eyy=21, ezz=22, exy=23, eyz=24, ezx=25,
+           srx=26, sry=27)
+
+
+class _Handle:
+    """What Calibration and Stereovision share: the handle's life, its stream."""
+
+    def __init__(self, device=0):
+        self._h = ctypes.c_void_p()
+        self._device = int(device)
+
+    def close(self):
+        if self._h:
+            capi.lib().oc_hip_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    set_stream = _Engine.set_stream
+    _adopt_stream_of = _Engine._adopt_stream_of
+    _stream_pinned = False
+    _auto_stream = None
+    _on_private_stream = True
+
+    def synchronize(self):
+        capi.check(capi.lib().oc_hip_synchronize(self._h))
+
+    def profile_enable(self, on=True):
+        capi.check(capi.lib().oc_hip_profile_enable(self._h, 1 if on else 0))
+
+    def profile_reset(self):
+        capi.check(capi.lib().oc_hip_profile_reset(self._h))
+
+    def profile_read(self):
+        ms = ctypes.c_double()
+        n = ctypes.c_long()
+        capi.check(capi.lib().oc_hip_profile_read(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
+
+    @staticmethod
+    def _rows(x, floats, what):
+        """(pointer, rows, stride in bytes, memory, keep-alive) of an (n, >= floats) float32 array / CUDA tensor whose rows
+        may be a view into a wider queue (only the last axis has to be contiguous)."""
+        if _is_torch(x):
+            import torch
+            if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] < floats or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+                raise ValueError("%s: need a CUDA float32 tensor of shape (n, >= %d) with contiguous rows" % (what, floats))
+            return ctypes.c_void_p(x.data_ptr()), x.shape[0], x.stride(0) * 4, capi.DEVICE, x
+        if not isinstance(x, np.ndarray) or x.dtype != np.float32 or x.ndim != 2 or x.shape[1] < floats or x.strides[1] != 4:
+            raise ValueError("%s: need a float32 array of shape (n, >= %d) with contiguous rows" % (what, floats))
+        return ctypes.c_void_p(x.ctypes.data), x.shape[0], x.strides[0], capi.HOST, x
+
+
+class Calibration(_Handle):
+    """Calibration(intrinsics, extrinsics) -- src/oc_calibration.h:47-97.  ``intrinsics``: fx, fy, fs, cx, cy, k1 ... k6,
+    p1, p2; ``extrinsics``: tx, ty, tz, rx, ry, rz.  The matrices are host arithmetic (no GPU needed); ``prepare(height,
+    width)`` builds the undistortion map on the device."""
+
+    def __init__(self, intrinsics, extrinsics, device=0):
+        super().__init__(device)
+        self.intrinsics = np.ascontiguousarray(intrinsics, dtype=np.float32).reshape(13)
+        self.extrinsics = np.ascontiguousarray(extrinsics, dtype=np.float32).reshape(6)
+        self.height = self.width = 0
+        capi.check(capi.lib().oc_hip_calibration_create(ctypes.c_void_p(self.intrinsics.ctypes.data),
+                                                        ctypes.c_void_p(self.extrinsics.ctypes.data), self._device,
+                                                        ctypes.byref(self._h)))
+
+    def _get(self, what, shape):
+        out = np.zeros(shape, dtype=np.float32)
+        capi.check(capi.lib().oc_hip_calibration_get(self._h, what, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    @property
+    def intrinsic_matrix(self):
+        return self._get(capi.CAL_INTRINSIC, (3, 3))
+
+    @property
+    def rotation_matrix(self):
+        return self._get(capi.CAL_ROTATION, (3, 3))
+
+    @property
+    def translation_vector(self):
+        return self._get(capi.CAL_TRANSLATION, (3,))
+
+    @property
+    def projection_matrix(self):
+        return self._get(capi.CAL_PROJECTION, (3, 4))
+
+    def set_undistortion(self, convergence, iteration):
+        capi.check(capi.lib().oc_hip_calibration_set_undistortion(self._h, float(convergence), int(iteration)))
+
+    def prepare(self, height, width):
+        capi.check(capi.lib().oc_hip_calibration_prepare(self._h, int(height), int(width)))
+        self.height, self.width = int(height), int(width)
+
+    def maps(self):
+        """(map_x, map_y) as float32 NumPy arrays of shape (height, width)."""
+        mx = np.empty((self.height, self.width), dtype=np.float32)
+        my = np.empty_like(mx)
+        capi.check(capi.lib().oc_hip_calibration_maps(self._h, ctypes.c_void_p(mx.ctypes.data), ctypes.c_void_p(my.ctypes.data), capi.HOST))
+        return mx, my
+
+    def undistort(self, points):
+        """Undistorted sensor coordinates of (n, 2) points: a new array / tensor of the same kind."""
+        self._adopt_stream_of(points)
+        out = points.clone() if _is_torch(points) else np.array(points, dtype=np.float32, order="C")
+        src = points if _is_torch(points) else out
+        p, n, stride, mem, _ = self._rows(src, 2, "undistort")
+        q, _, stride_out, _, _ = self._rows(out, 2, "undistort")
+        if stride_out != stride:
+            raise ValueError("undistort: rows of the points must be contiguous")
+        capi.check(capi.lib().oc_hip_calibration_undistort(self._h, p, q, n, stride, mem))
+        return out
+
+
+class Stereovision(_Handle):
+    """Stereovision(view1_cam, view2_cam) -- src/oc_stereovision.h.  Both ``Calibration`` objects are kept alive by this one."""
+
+    def __init__(self, view1_cam, view2_cam, thread_number=1):
+        super().__init__(view1_cam._device)
+        self.view1_cam, self.view2_cam = view1_cam, view2_cam
+        self.thread_number = thread_number
+        capi.check(capi.lib().oc_hip_stereo_create(view1_cam._h, view2_cam._h, ctypes.byref(self._h)))
+
+    def close(self):
+        super().close()  # before the cameras it points to
+
+    @property
+    def fundamental_matrix(self):
+        F = np.zeros((3, 3), dtype=np.float32)
+        capi.check(capi.lib().oc_hip_stereo_fundamental(self._h, ctypes.c_void_p(F.ctypes.data)))
+        return F
+
+    def reconstruct(self, view1_points, view2_points):
+        """(n, 3) world coordinates of (n, 2) point pairs (rows may be views into a wider queue)."""
+        self._adopt_stream_of(view1_points)
+        p1, n, s1, mem, _ = self._rows(view1_points, 2, "reconstruct")
+        p2, n2, s2, mem2, _ = self._rows(view2_points, 2, "reconstruct")
+        if n != n2 or mem != mem2:
+            raise ValueError("reconstruct: the two point queues differ in length or memory space")
+        if mem == capi.DEVICE:
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float32, device=view1_points.device)
+            po = ctypes.c_void_p(out.data_ptr())
+        else:
+            out = np.empty((n, 3), dtype=np.float32)
+            po = ctypes.c_void_p(out.ctypes.data)
+        capi.check(capi.lib().oc_hip_stereo_reconstruct(self._h, p1, s1, p2, s2, po, 12, n, mem))
+        return out
+
+    def reconstruct_pois(self, pois):
+        """ref_coor, tar_coor and deformation = tar_coor - ref_coor of every POI2DS record, in place."""
+        self._adopt_stream_of(pois)
+        p, n, stride, mem, _ = self._rows(pois, capi.POI2DS_FLOATS, "reconstruct_pois")
+        capi.check(capi.lib().oc_hip_stereo_reconstruct_pois(self._h, p, n, stride, mem))
+        return pois
 
 
 class RegionFit:

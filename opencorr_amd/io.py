@@ -8,6 +8,9 @@ against files produced by the reference and vice versa:
   ``x,y,u,v,u0,v0,ZNCC,iteration,convergence,feature,exx,eyy,exy,subset_rx,subset_ry,``
 * ``IO2D::saveDeformationTable2D``               src/oc_io.cpp:347-392
   ``x,y,u,ux,uy,uxx,uxy,uyy,v,vx,vy,vxx,vxy,vyy,subset_rx,subset_ry,``
+* ``IO2D::saveTable2DS / loadTable2DS``          src/oc_io.cpp:506-672 -- the stereo table, the 28 floats of a POI2DS record
+  in record order: ``x,y,u,v,w,r1r2 ZNCC,r1t1 ZNCC,r1t2 ZNCC,r2_x,r2_y,t1_x,t1_y,t2_x,t2_y,ref_x,ref_y,ref_z,tar_x,tar_y,
+  tar_z,exx,eyy,ezz,exy,eyz,ezx,subset_rx,subset_ry,``
 * ``IO3D::saveTable3D / loadTable3D``            src/oc_io.cpp:1004-1089
 * ``Image3D::loadBin``                           src/oc_image.cpp:76-110 -- ``int32[3]`` header
   (dim_x, dim_y, dim_z) followed by dim_z*dim_y*dim_x float32, x fastest.
@@ -25,6 +28,10 @@ TABLE2D = [("x", 0), ("y", 1), ("u", 2), ("v", 8), ("u0", 14), ("v0", 15), ("ZNC
            ("subset_ry", 24)]
 DEFORMATION2D = [("x", 0), ("y", 1)] + [(n, 2 + i) for i, n in enumerate(
     ["u", "ux", "uy", "uxx", "uxy", "uyy", "v", "vx", "vy", "vxx", "vxy", "vyy"])] + [("subset_rx", 23), ("subset_ry", 24)]
+# POI2DS record (src/oc_poi.h:140-183): the table's columns are the record's floats in order
+TABLE2DS = [(n, i) for i, n in enumerate(
+    ["x", "y", "u", "v", "w", "r1r2 ZNCC", "r1t1 ZNCC", "r1t2 ZNCC", "r2_x", "r2_y", "t1_x", "t1_y", "t2_x", "t2_y", "ref_x", "ref_y",
+     "ref_z", "tar_x", "tar_y", "tar_z", "exx", "eyy", "ezz", "exy", "eyz", "ezx", "subset_rx", "subset_ry"])]
 # POI3D record (src/oc_poi.h:187-222): x y z | u ux uy uz v vx vy vz w wx wy wz | u0 v0 w0 zncc iter conv feature | e[6] | r[3]
 TABLE3D = [("x", 0), ("y", 1), ("z", 2), ("u", 3), ("v", 7), ("w", 11), ("u0", 15), ("v0", 16), ("w0", 17), ("ZNCC", 18),
            ("iteration", 19), ("convergence", 20), ("feature", 21), ("ux", 4), ("uy", 5), ("uz", 6), ("vx", 8), ("vy", 9),
@@ -48,7 +55,7 @@ def _load(path, columns, floats, delimiter):
     # every row fills the fields it has (a short or truncated line leaves ITS remaining fields at 0, like the C++ twin
     # include/opencorr_compat/oc_io.h does; it must not cost the other rows their columns); rows without a position
     # (fewer than 2 / 3 values) are skipped there as well
-    need = 2 if floats == 25 else 3
+    need = 3 if floats == 31 else 2
     rows = [r for r in rows if len(r) >= need]
     pois = np.zeros((len(rows), floats), dtype=np.float32)
     for i, r in enumerate(rows):
@@ -70,6 +77,17 @@ def load_table2d(path, delimiter=","):
 def save_deformation_table2d(path, pois, delimiter=","):
     """IO2D::saveDeformationTable2D: the full 12-parameter deformation vector per POI."""
     _save(path, pois, DEFORMATION2D, delimiter)
+
+
+def save_table2ds(path, pois, delimiter=","):
+    """IO2D::saveTable2DS: one row per POI2DS record (n x 28 float32)."""
+    _save(path, pois, TABLE2DS, delimiter)
+
+
+def load_table2ds(path, delimiter=","):
+    """IO2D::loadTable2DS -> (n, 28) float32 POI2DS records.  The reference's own example table
+    (examples/3d_dic/GT4-0273_0_epipolar_sift_r16.csv) has 26 columns: the subset radius stays 0."""
+    return _load(path, TABLE2DS, 28, delimiter)
 
 
 def save_table3d(path, pois, delimiter=","):
