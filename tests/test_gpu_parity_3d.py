@@ -8,6 +8,8 @@ the reference itself: its DVC example volumes are not in the mount.
 import numpy as np
 import pytest
 
+from icgn3d_launch_shape import SWEEP_RADII
+
 pytestmark = pytest.mark.gpu
 
 SHAPE = (72, 76, 80)  # dz, dy, dx
@@ -416,20 +418,27 @@ def big_volumes():
     return ref, tar, oracle.Prepared3D(ref, tar)
 
 
-def _icgn3d_case(big_volumes, r, pois, stop=20.0):
+def _icgn3d_case(big_volumes, r, pois, stop=20.0, fma=0, lengths=None):
+    """``r``: one radius or (rx, ry, rz); ``fma``: the arithmetic mode (and the oracle order that goes with it); ``lengths``:
+    the queue is also run cut to these lengths (default: whole)."""
     import opencorr_amd
     import oracle
     ref, tar, prep = big_volumes
+    rx, ry, rz = (r, r, r) if np.isscalar(r) else r
     want = pois.copy()
-    oracle.icgn3d1(prep, r, r, r, 0.001, stop, want, order=oracle.GPU_ORDER_3D, lanes=oracle.GPU_LANES_3D)
-    icgn = opencorr_amd.ICGN3D1(r, r, r, 0.001, stop)
+    oracle.icgn3d1(prep, rx, ry, rz, 0.001, stop, want, order=oracle.ORDER_LANES_FMA if fma else oracle.GPU_ORDER_3D,
+                   lanes=oracle.GPU_LANES_3D)
+    icgn = opencorr_amd.ICGN3D1(rx, ry, rz, 0.001, stop)
     icgn.set_images(ref, tar)
     icgn.prepare()
-    got = icgn.compute(pois.copy())
+    if fma:
+        icgn.set_tuning("arith_fma", 1)
     P = oracle.P3
-    assert np.array_equal(got[:, P["iteration"]], want[:, P["iteration"]])
-    mism = np.argwhere(_bits(got) != _bits(want))
-    assert mism.size == 0, "first mismatches (poi, field): %s" % mism[:10].tolist()
+    for n in lengths or [len(pois)]:
+        got = icgn.compute(pois[:n].copy())
+        assert np.array_equal(got[:, P["iteration"]], want[:n, P["iteration"]])
+        mism = np.argwhere(_bits(got) != _bits(want[:n]))
+        assert mism.size == 0, "first mismatches (poi, field): %s" % mism[:10].tolist()
     return want
 
 
@@ -529,6 +538,54 @@ def test_icgn3d1_global_tap_fallback(big_volumes):
     pois = pois.astype(np.float32)
     want = _icgn3d_case(big_volumes, 16, pois, stop=6.0)
     assert np.isfinite(want[:, P["u"]]).all()
+
+
+def _sweep_queue(r):
+    """15 records for radii ``r`` on the BIG pair: two POIs whose guess carries a 0.3 stretch along x (some passes of their
+    sweeps overflow the staged box and take global taps inside that launch shape), one next to a face, one rejected, one
+    NaN, ten ordinary ones with integer and non-integer centres.  The specials come first: a queue cut to 12 holds them all,
+    a queue of one is a stretched POI."""
+    import oracle
+    from opencorr_amd import synth
+    rx, ry, rz = r
+    dz, dy, dx = BIG
+    P = oracle.P3
+    rng = np.random.default_rng(7000 + 10000 * rx + 100 * ry + rz)
+    lo, hi = (rx + 4, ry + 4, rz + 4), (dx - rx - 5, dy - ry - 5, dz - rz - 5)
+    c = [rng.uniform(lo[a], hi[a], 10) for a in range(3)]
+    for a in range(3):
+        c[a][::2] = np.floor(c[a][::2])
+    cx, cy, cz = dx // 2, dy // 2, dz // 2
+    xs = np.concatenate([[cx, cx - 1.5, rx, cx, cx], c[0]])
+    ys = np.concatenate([[cy, cy + 0.5, cy, cy, cy], c[1]])
+    zs = np.concatenate([[cz, cz - 0.25, cz, cz, cz], c[2]])
+    pois = oracle.make_pois3d(xs, ys, zs)
+    w = synth.DEFAULT_WARP_3D
+    pois[:, P["u"]], pois[:, P["v"]], pois[:, P["w"]] = round(w["u"]), round(w["v"]), round(w["w"])  # integer guess, as FFTCC gives
+    pois[0, P["ux"]] = 0.3
+    pois[1, P["ux"]] = -0.3
+    pois[1, P["wy"]] = 0.05
+    pois[3, P["zncc"]] = -1.0    # rejected on entry, flag preserved
+    pois[4, P["v"]] = np.nan
+    return pois.astype(np.float32)
+
+
+@pytest.mark.parametrize("fma", [0, 1])
+@pytest.mark.parametrize("r", SWEEP_RADII, ids=lambda r: "r%d_%d_%d" % r)
+def test_icgn3d1_launch_shape_sweep(big_volumes, r, fma):
+    """Every (row pitch, samples_per_pass, fits) that launch_icgn3d1 can pick for radii 3 ... 32 (tests/icgn3d_launch_shape.py;
+    tests/test_icgn3d_launch_shapes.py asserts that the list reaches them all): every float identical to the oracle in the
+    kernel's summation order, in both arithmetic modes, for queues of 1, 12 and 15 records.  stop = 6 bounds the stretched
+    POIs, which do not converge."""
+    import oracle
+    P = oracle.P3
+    pois = _sweep_queue(r)
+    want = _icgn3d_case(big_volumes, r, pois, stop=6.0, fma=fma, lengths=[1, 12, len(pois)])
+    assert want[3, P["zncc"]] == -1.0 and want[4, P["zncc"]] == -3.0
+    # the POI next to the face and the ordinary ones are iterated to the end: converged, or stop-limited (-4: the smallest
+    # subvolumes hold too few speckles for six iterations to reach 1e-3), never rejected and never out of the volume
+    z = want[[2] + list(range(5, len(want))), P["zncc"]]
+    assert ((z > 0.9) | (z == -4.0)).all(), z
 
 
 def test_compute_chain_3d_matches_separate_calls(volumes):
