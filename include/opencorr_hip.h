@@ -335,6 +335,14 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *   "icgn2d_xcd"      1 (default): workgroups of one XCD serve a contiguous range of the POI queue
  *   "icgn2d_tile_px"  side of the square image tiles the ICGN2D / NR2D1 queue is visited by (L1 / L2 locality; default 128;
  *                     0 = queue order; applied to queues >= 16384 POIs)
+ *   "icgn2d_setup_cache"  1 (default): ICGN2D1 / ICGN2D2 keep the per-POI set-up of their big-queue launches (variants 5 / 4) --
+ *                     reference mean, norm and inverse Hessian: 152 + 8 B per POI at 6 DoF, 584 + 8 B at 12 -- from one compute()
+ *                     to the next and start from it while reference, gradients, radii, arithmetic, count, stride and the
+ *                     queue's (x, y) stay what they were: the sequence "overwrite the target in place, prepare_tar(), compute()"
+ *                     pays for the set-up once.  set_images / share_images / prepare_ref and any change of those settings make
+ *                     the next call rebuild it; the coordinates are compared on the device, no call waits for the host.
+ *                     Centre offsets, self-adaptive radii, IC-LM and smaller queues never use it.  0: every call computes its
+ *                     set-up.  Same bits either way (oc_hip_icgn2d_setup_cache_last tells which way a call went)
  *   "icgn2d_split_chunks"  A/B build, variant 8 only: chunks of the two-stream pipeline (0 = the two kernels back to back)
  *   "fftcc2d_fused"   1 (default): single-kernel FFTCC2D (register / LDS FFT) for EVERY window with both radii in 4 ... 32 (even
  *                     sides 8 ... 64): a template instance per square side and for the 42 rectangular pairs (radius_x !=
@@ -434,6 +442,13 @@ int oc_hip_read_field(oc_hip_engine* engine, const char* name, float* host_dst, 
 int oc_hip_profile_enable(oc_hip_engine* engine, int enable);
 int oc_hip_profile_read(oc_hip_engine* engine, double* total_ms, long* launches);
 int oc_hip_profile_reset(oc_hip_engine* engine);
+/* How the engine's last ICGN2D compute() treated the set-up cache ("icgn2d_setup_cache"): OC_HIP_SETUP_CACHE_NONE = it went
+ * around the cache, _FILL = it computed every POI's set-up and filed it, _USE = it started from the filed records.
+ * Waits for the engine's work (the coordinate comparison happens on the device). */
+#define OC_HIP_SETUP_CACHE_NONE 0
+#define OC_HIP_SETUP_CACHE_FILL 1
+#define OC_HIP_SETUP_CACHE_USE 2
+int oc_hip_icgn2d_setup_cache_last(oc_hip_engine* engine, int* state);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ CALIBRATION, STEREOVISION = 11, 12
 POI2D_BYTES, POI3D_BYTES, POI2DS_BYTES = 100, 124, 112
 POI2D_FLOATS, POI3D_FLOATS, POI2DS_FLOATS = 25, 31, 28
 POI2DS = 22  # the `ndim` of oc_hip_strain_prepare / oc_hip_strain_compute that selects POI2DS records
+SETUP_CACHE_NONE, SETUP_CACHE_FILL, SETUP_CACHE_USE = 0, 1, 2  # oc_hip_icgn2d_setup_cache_last
 CAL_INTRINSIC, CAL_ROTATION, CAL_TRANSLATION, CAL_PROJECTION = 0, 1, 2, 3
 
 # every symbol include/opencorr_hip.h declares (tests check the .so exports them all)
@@ -38,7 +39,7 @@ SYMBOLS = [
     "oc_hip_compute", "oc_hip_compute_chain", "oc_hip_compute_one", "oc_hip_compute_with_offsets", "oc_hip_compute_one_with_offset", "oc_hip_single_stats",
     "oc_hip_set_self_adaptive", "oc_hip_synchronize", "oc_hip_select_best", "oc_hip_split_reliable", "oc_hip_merge_recovered",
     "oc_hip_get_kind", "oc_hip_get_field", "oc_hip_read_field",
-    "oc_hip_profile_enable", "oc_hip_profile_read", "oc_hip_profile_reset",
+    "oc_hip_profile_enable", "oc_hip_profile_read", "oc_hip_profile_reset", "oc_hip_icgn2d_setup_cache_last",
     "oc_hip_set_devices", "oc_hip_get_devices", "oc_hip_group_queue",
     "oc_hip_calibration_create", "oc_hip_calibration_set_undistortion", "oc_hip_calibration_prepare", "oc_hip_calibration_get",
     "oc_hip_calibration_maps", "oc_hip_calibration_undistort",
@@ -169,6 +170,7 @@ def lib():
     L.oc_hip_profile_enable.argtypes = [vp, i]
     L.oc_hip_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.oc_hip_profile_reset.argtypes = [vp]
+    L.oc_hip_icgn2d_setup_cache_last.argtypes = [vp, ctypes.POINTER(i)]
     L.oc_hip_set_devices.argtypes = [vp, ctypes.POINTER(i), i]
     L.oc_hip_get_devices.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(i)]
     L.oc_hip_group_queue.argtypes = [vp, i, pp, ctypes.POINTER(sz)]

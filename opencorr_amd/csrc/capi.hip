@@ -172,15 +172,21 @@ int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
 
 // Locality schedule of a 2D queue (poi_order.hip): worth four tiny kernels once the queue is much larger than what
 // is in flight.  *perm = nullptr when the queue is short or the schedule is switched off.
-int tile_order(oc_hip_engine* e, const float* pois, int stride_f, size_t n, const unsigned** perm) {
+// xy_copy (ICGN2D set-up cache): the coordinate check rides in the schedule's first pass, or runs as one small kernel of its own
+// when there is no schedule.
+int tile_order(oc_hip_engine* e, const float* pois, int stride_f, size_t n, const unsigned** perm, unsigned* xy_copy = nullptr,
+               unsigned* xy_word = nullptr, unsigned xy_epoch = 0) {
     *perm = nullptr;
-    if (e->icgn2d_tile_px <= 0 || n < 16384) return OC_HIP_OK;
+    if (e->icgn2d_tile_px <= 0 || n < 16384) {
+        if (xy_copy) OC_HIP_TRY(ochip::launch_poi2d_xy_check(pois, stride_f, n, xy_copy, xy_word, xy_epoch, e->stream));
+        return OC_HIP_OK;
+    }
     const ImagePair& im = *e->img;
     OC_TRY(e->perm.reserve(n * sizeof(unsigned)));
     OC_TRY(e->tiles.reserve(ochip::poi2d_tile_count(im.dy, im.dx, e->icgn2d_tile_px) * sizeof(unsigned)));
     OC_TRY(e->perm_slots.reserve(n * sizeof(unsigned)));
     OC_HIP_TRY(ochip::launch_poi2d_tile_order(pois, stride_f, n, im.dy, im.dx, e->icgn2d_tile_px, e->tiles.as<unsigned>(),
-                                              e->perm_slots.as<unsigned>(), e->perm.as<unsigned>(), e->stream));
+                                              e->perm_slots.as<unsigned>(), e->perm.as<unsigned>(), e->stream, xy_copy, xy_word, xy_epoch));
     *perm = e->perm.as<unsigned>();
     return OC_HIP_OK;
 }
@@ -267,12 +273,55 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     }
     // one wave per POI; grid.x is limited to 2^31-1
     const size_t kMaxGrid = 1u << 30;
+    // Set-up cache: the big-queue table variants keep { reference mean, norm, H^-1 } per POI from call to call (icgn2d.hip CACHE).
+    // A sequence that correlates many targets against one reference over one grid -- overwrite the target, prepare_tar(),
+    // compute() -- pays for the set-up once.  The host decides what it can know (the key); whether the queue still holds the
+    // coordinates the records were built for is decided on the device by the check in front of the launch.  Centre offsets,
+    // self-adaptive radii, IC-LM and the small-queue variants go around it.
+    e->setup_cache_last = 0;
+    const bool cached = e->icgn2d_setup_cache && !lm && !band && !d_offsets && !e->self_adaptive && (variant == 4 || variant == 5) &&
+                        count <= kMaxGrid;
+    oc_hip_engine::SetupCacheKey cache_key;
+    bool cache_hit = false;
+    unsigned *cache_xy = nullptr, *cache_word = nullptr;
+    if (cached) {
+        const void *r0 = e->setup_cache_recs.p, *x0 = e->setup_cache_xy.p;
+        OC_TRY(e->setup_cache_recs.reserve(count * (size_t)ochip::icgn2d_setup_record_floats(dof) * sizeof(float)));
+        OC_TRY(e->setup_cache_xy.reserve(count * 2 * sizeof(unsigned)));
+        if (!e->setup_cache_word.p) {
+            OC_TRY(e->setup_cache_word.reserve(256));
+            OC_HIP_TRY(hipMemsetAsync(e->setup_cache_word.p, 0, 256, e->stream));
+            e->setup_cache_epoch = 0;
+        }
+        cache_key.count = count;
+        cache_key.stride_f = stride_f;
+        cache_key.variant = variant;
+        cache_key.dof = dof;
+        cache_key.rx = rx;
+        cache_key.ry = ry;
+        cache_key.arith_fma = e->arith_fma;
+        cache_key.height = im.dy;
+        cache_key.width = im.dx;
+        cache_key.ref = im.ref_ptr();
+        cache_key.gx = e->gx.p;
+        cache_key.gy = e->gy.p;
+        cache_key.ref_generation = e->ref_generation;
+        cache_hit = e->setup_cache_valid && cache_key == e->setup_cache_key && r0 == e->setup_cache_recs.p && x0 == e->setup_cache_xy.p;
+        e->setup_cache_valid = false;  // (until this call's launch is enqueued: an error exit leaves records and coordinates apart)
+        if (++e->setup_cache_epoch == 0) e->setup_cache_epoch = 1;
+        cache_xy = e->setup_cache_xy.as<unsigned>();
+        cache_word = e->setup_cache_word.as<unsigned>();
+        P.cache_recs = e->setup_cache_recs.as<float>();
+        P.cache_word = cache_word;
+        P.cache_epoch = e->setup_cache_epoch;
+        P.cache_force_fill = cache_hit ? 0 : 1;
+    }
     for (size_t first = 0; first < count; first += kMaxGrid) {
         const size_t n = (count - first) < kMaxGrid ? (count - first) : kMaxGrid;
         float* pois = d_pois + first * (size_t)stride_f;
         if (d_offsets) P.offsets = d_offsets + 2 * first;
         if (P.setup) P.setup = e->setup_recs.as<float>() + first * (size_t)ochip::icgn2d_setup_record_floats(dof);
-        OC_TRY(tile_order(e, pois, stride_f, n, &P.perm));
+        OC_TRY(tile_order(e, pois, stride_f, n, &P.perm, cache_xy, cache_word, P.cache_epoch));
         ProfScope prof(e);  // the solver kernel alone (what rocprofv3 reports for it)
         hipError_t err;
         if (variant == 8 && !lm && e->icgn2d_split_chunks >= 2 && n >= 16384) {
@@ -325,6 +374,11 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
             err = dof == 6 ? ochip::launch_icgn2d1(P, pois, stride_f, n, variant, e->icgn2d_xcd != 0, e->stream)
                            : ochip::launch_icgn2d2(P, pois, stride_f, n, variant, e->icgn2d_xcd != 0, e->stream);
         if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "ICGN2D kernel launch failed: %s", hipGetErrorString(err));
+    }
+    if (cached) {
+        e->setup_cache_key = cache_key;
+        e->setup_cache_valid = true;
+        e->setup_cache_last = cache_hit ? 2 : 1;
     }
     return OC_HIP_OK;
 }
@@ -628,6 +682,7 @@ static int replicate_images(oc_hip_engine* leader, oc_hip_engine* r) {
         r->img = img;
     }
     r->ref_ready = r->tar_ready = false;
+    r->ref_generation++;
     return OC_HIP_OK;
 }
 
@@ -672,6 +727,7 @@ int oc_hip_set_images2d(oc_hip_engine* e, const float* ref, const float* tar, in
     OC_HIP_TRY(hipStreamSynchronize(e->stream));  // host buffers may be released by the caller
     e->img = img;
     e->ref_ready = e->tar_ready = false;
+    e->ref_generation++;  // (the ICGN2D set-up cache belongs to the previous reference)
     for (oc_hip_engine* r : e->replicas) OC_TRY(replicate_images(e, r));
     return OC_HIP_OK;
 }
@@ -715,6 +771,7 @@ int oc_hip_share_images(oc_hip_engine* e, oc_hip_engine* donor) {
     std::lock_guard<std::mutex> lock(e->mu);
     e->img = donor->img;
     e->ref_ready = e->tar_ready = false;
+    e->ref_generation++;
     // members of a group: share with the donor's member on the same device when there is one, copy otherwise
     for (oc_hip_engine* r : e->replicas) {
         oc_hip_engine* twin = nullptr;
@@ -726,6 +783,7 @@ int oc_hip_share_images(oc_hip_engine* e, oc_hip_engine* donor) {
             std::lock_guard<std::mutex> rlock(r->mu);
             r->img = twin->img;
             r->ref_ready = r->tar_ready = false;
+            r->ref_generation++;
         } else {
             OC_TRY(replicate_images(e, r));
         }
@@ -747,6 +805,7 @@ static int clone_engine(const oc_hip_engine* e, int device, oc_hip_engine** out)
     r->icgn2d_xcd = e->icgn2d_xcd;
     r->arith_fma = e->arith_fma;
     r->icgn2d_split_chunks = e->icgn2d_split_chunks;
+    r->icgn2d_setup_cache = e->icgn2d_setup_cache;
     r->fftcc2d_fused = e->fftcc2d_fused;
     r->fftcc3d_fused = e->fftcc3d_fused;
     r->fftcc3d_planes_blocks = e->fftcc3d_planes_blocks;
@@ -775,8 +834,10 @@ static int rehome(oc_hip_engine* e, int device) {
     for (DevBuf* b : {&e->gx, &e->gy, &e->gz, &e->coef, &e->coef_gx, &e->coef_gy, &e->tmp, &e->poi_stage, &e->off_stage, &e->cursors,
                       &e->perm, &e->tiles, &e->perm_slots, &e->split_scratch, &e->split_tmp, &e->prefilter_tmp, &e->st_box, &e->st_counts, &e->st_start, &e->st_cursor, &e->st_slots,
                       &e->st_order, &e->st_recs, &e->st_fallback, &e->win, &e->freq, &e->norms, &e->flags, &e->group_mirror,
-                      &e->group_off_mirror})
+                      &e->group_off_mirror, &e->setup_cache_recs, &e->setup_cache_xy, &e->setup_cache_word})
         b->release();
+    e->setup_cache_valid = false;
+    e->setup_cache_last = 0;
     e->img.reset();
     e->ref_ready = e->tar_ready = false;
     e->st_count = 0;
@@ -996,6 +1057,9 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
 #endif
         if (value < 0 || value > 256) return fail(OC_HIP_ERR_INVALID, "icgn2d_split_chunks must be 0 (back to back) ... 256");
         e->icgn2d_split_chunks = value;
+    } else if (k == "icgn2d_setup_cache") {
+        // 1 = the big-queue ICGN2D1 / ICGN2D2 launches keep their set-up records from call to call, 0 = every call computes them
+        e->icgn2d_setup_cache = value != 0;
     } else if (k == "icgn2d_tile_px") {
         if (value < 0 || (value > 0 && value < 16)) return fail(OC_HIP_ERR_INVALID, "icgn2d_tile_px must be 0 (off) or >= 16");
         e->icgn2d_tile_px = value;
@@ -1066,6 +1130,7 @@ int oc_hip_prepare_ref(oc_hip_engine* e) {
                                         e->gz.as<float>(), e->stream));
     }
     e->ref_ready = true;
+    e->ref_generation++;  // an image used in place may hold new pixels: the gradients are new, and so is every ICGN2D set-up record
     OC_TRY(mark_tail(e));
     for (oc_hip_engine* r : e->replicas) OC_TRY(oc_hip_prepare_ref(r));
     OC_HIP_TRY(hipSetDevice(e->device));
@@ -1489,6 +1554,21 @@ int oc_hip_profile_reset(oc_hip_engine* e) {
     std::lock_guard<std::mutex> lock(e->mu);
     OC_HIP_TRY(hipStreamSynchronize(e->stream));
     clear_events(e);
+    return OC_HIP_OK;
+}
+
+int oc_hip_icgn2d_setup_cache_last(oc_hip_engine* e, int* state) {
+    OC_ACTIVATE(e);
+    if (!state) return fail(OC_HIP_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(e->mu);
+    *state = e->setup_cache_last;
+    if (e->setup_cache_last == 2) {
+        // the coordinate check decided on the device: a word that carries the launch's epoch made it a fill call
+        drain_engine(e);
+        unsigned word = 0;
+        OC_HIP_TRY(hipMemcpy(&word, e->setup_cache_word.p, sizeof(word), hipMemcpyDeviceToHost));
+        *state = word == e->setup_cache_epoch ? OC_HIP_SETUP_CACHE_FILL : OC_HIP_SETUP_CACHE_USE;
+    }
     return OC_HIP_OK;
 }
 

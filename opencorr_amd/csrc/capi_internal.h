@@ -186,6 +186,27 @@ struct oc_hip_engine {
     DevBuf cursors;  // small device scratch (batch maxima)
     DevBuf perm, tiles, perm_slots;  // locality schedule of the ICGN2D queue (poi_order.hip)
     DevBuf setup_recs;               // icgn2d variant 8 (split launch shape): mean, norm, H^-1 per POI between the two kernels
+    // ICGN2D set-up cache (run_icgn2d, icgn2d.hip CACHE): { reference mean, norm, H^-1 } per POI of the last big-queue launch, the
+    // (x, y) bit patterns they were built for, and the word the coordinate check stamps.  What the host can know -- reference
+    // and its gradients re-prepared, radii, arithmetic, count, stride, variant -- lives in setup_cache_key; the coordinates are
+    // compared on the device, so no call waits for the host.  Grow-only, per engine (group members own theirs).
+    DevBuf setup_cache_recs, setup_cache_xy, setup_cache_word;
+    struct SetupCacheKey {
+        size_t count = 0;
+        int stride_f = 0, variant = -1, dof = 0, rx = 0, ry = 0, arith_fma = 0, height = 0, width = 0;
+        const void *ref = nullptr, *gx = nullptr, *gy = nullptr;
+        unsigned long long ref_generation = 0;
+        bool operator==(const SetupCacheKey& o) const {
+            return count == o.count && stride_f == o.stride_f && variant == o.variant && dof == o.dof && rx == o.rx && ry == o.ry &&
+                   arith_fma == o.arith_fma && height == o.height && width == o.width && ref == o.ref && gx == o.gx && gy == o.gy &&
+                   ref_generation == o.ref_generation;
+        }
+    } setup_cache_key;
+    bool setup_cache_valid = false;          // the records belong to setup_cache_key
+    unsigned long long ref_generation = 0;   // bumped by set_images / share_images / prepare_ref: the reference or its gradients changed
+    unsigned setup_cache_epoch = 0;          // one per cached launch; the coordinate check stamps the word with it
+    int setup_cache_last = 0;                // last run_icgn2d: 0 = went around the cache, 1 = fill (host's decision), 2 = the device word decided
+    int icgn2d_setup_cache = 1;              // "icgn2d_setup_cache" tuning key: 0 = every call computes its set-up (the behaviour before the cache)
     DevBuf split_scratch, split_tmp; // oc_hip_split_reliable / oc_hip_merge_recovered (poi_split.hip)
     // Strain (src/oc_strain.cpp:31-46: radius, min neighbours; ZNCC threshold 0.9, Cauchy approximation)
     float st_radius = 0.f, st_zncc = 0.9f;

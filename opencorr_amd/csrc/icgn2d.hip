@@ -177,6 +177,18 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     // barriers, which every wave passes exactly once -- also the ones that abandon their POI early (leave())
     constexpr bool COOP = MODE == 4 && DOF == 6 && LM == 0 && WPB == 8 && PHASE != 2;
     constexpr bool kSetupOnly = PHASE == 1, kIterOnly = PHASE == 2;
+    // Set-up cache (the big-queue table variants 4 and 5, no centre offsets): mean, norm and H^-1 of a POI depend on the reference
+    // image, the POI's x, y and the radii only, so a sequence of compute() calls over one reference and one grid needs them
+    // once.  P.cache_recs != nullptr makes the launch either a FILL call -- the set-up as ever, plus the POI's record (the
+    // PHASE 1 layout) -- or a USE call, which starts from the record (as PHASE 2 does) and skips the reference pass, the
+    // Hessian sweep, the reduction and the inverse: same values, same bits.  The choice is GRID-UNIFORM: a kernel argument
+    // (the host knows the records are stale) or one device word that the coordinate check in front of this launch
+    // (poi_order.hip) stamps with this launch's epoch when any POI's x, y differ from the ones the records were built
+    // for.  In a USE launch NO wave executes COOP's two barriers (leave() included); the table-fill barrier stays.  In a
+    // FILL launch a wave that fails only the data part of the guard (u, v, zncc) still runs the set-up and files its record
+    // -- it passes COOP's barriers on the ordinary path, before any sweep barrier -- so that invariant (b) below holds in
+    // both kinds of launch and a POI rejected now finds its record when a later call accepts it.
+    constexpr bool CACHE = MODE == 4 && LM == 0 && PHASE == 0 && WPB == 8 && OFFS == 0;
     constexpr int kSetupFloats = icgn2d_setup_floats(DOF);
     // lockstep sweeps (see OC_SWEEP_BARRIER above): the 8-wave table variants -- one subset size per launch, so every live
     // wave of a workgroup runs the same number of pass groups
@@ -211,6 +223,13 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     const int NTA = L.nt;  // passes the LDS arrays are sized for (>= the passes of any POI)
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    bool cache_fill = false, cache_use = false;
+    if constexpr (CACHE) {
+        if (P.cache_recs) {
+            cache_fill = P.cache_force_fill != 0 || (unsigned)__builtin_amdgcn_readfirstlane((int)*P.cache_word) == P.cache_epoch;
+            cache_use = !cache_fill;
+        }
+    }
     [[maybe_unused]] unsigned long long tl_mark = __builtin_readcyclecounter();
     [[maybe_unused]] unsigned long long tl[4] = {0, 0, 0, 0};
     auto lap = [&](int slot) {
@@ -223,6 +242,7 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     };
     auto leave = [&]() {
         if constexpr (COOP) {
+            if (cache_use) return;  // (grid-uniform: nobody is at COOP's barriers in a launch that starts from the records)
             if (lane < 24) coop_area[wave * 64 + lane] = 0.f;
             __syncthreads();
             if (wave == 0) coop_inverse6_x8(coop_area, lane);
@@ -288,8 +308,10 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     }
 
     // guard, src/oc_icgn.cpp:160-167 (2D2: 705-712)
-    if (py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1 || fabsf(u_in) >= width ||
-        fabsf(v_in) >= height || zncc_in < 0 || isnan(u_in) || isnan(v_in)) {
+    // (the geometric part decides whether the POI has a set-up at all; the data part is what a later call may see differently)
+    const bool guard_geo = py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1;
+    const bool guard_data = fabsf(u_in) >= width || fabsf(v_in) >= height || zncc_in < 0 || isnan(u_in) || isnan(v_in);
+    if (guard_geo || (guard_data && !cache_fill)) {
         if (lane == 0) poi[poi2d::ZNCC] = zncc_in >= 0 ? -3.f : zncc_in;
         leave();
         return;
@@ -317,8 +339,10 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     float ref_norm, ref_mean;
     const int x0r = (int)(px - rx), y0r = (int)(py - ry);
     const unsigned roff = (unsigned)__builtin_amdgcn_readfirstlane((y0r * width + x0r) * 4);
-    float* const setup_rec = (kSetupOnly || kIterOnly) ? P.setup + idx * (unsigned long long)kSetupFloats : nullptr;
-    if constexpr (kIterOnly) {
+    float* const setup_rec = (kSetupOnly || kIterOnly) ? P.setup + idx * (unsigned long long)kSetupFloats
+                             : (CACHE && (cache_fill || cache_use)) ? P.cache_recs + idx * (unsigned long long)kSetupFloats
+                                                                     : nullptr;
+    if (kIterOnly || cache_use) {
         ref_mean = uni(setup_rec[0]);
         ref_norm = uni(setup_rec[1]);
     } else if constexpr (kSetupOnly) {
@@ -374,7 +398,7 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     // ---- steepest-descent image + Hessian (src/oc_icgn.cpp:179-207; 2D2: 716-756), inverse (:210 / :759)
     float hinv_col[DOF];  // lane j < DOF: column j of H^-1
     float hcol[LM ? DOF : 1];  // LM: column j of H itself
-    if constexpr (!kIterOnly) {
+    if (!kIterOnly && !cache_use) {
         float h[NH];
 #pragma unroll
         for (int i = 0; i < NH; i++) h[i] = 0.f;
@@ -529,10 +553,12 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
             }
         }
         return;
-    } else if constexpr (kIterOnly) {
-        const float* __restrict__ row = setup_rec + 2 + min(lane, DOF - 1) * DOF;
+    } else if (kIterOnly || cache_use) {
+        if constexpr (!LM) {
+            const float* __restrict__ row = setup_rec + 2 + min(lane, DOF - 1) * DOF;
 #pragma unroll
-        for (int j = 0; j < DOF; j++) hinv_row[j] = lane < DOF ? row[j] : 0.f;
+            for (int j = 0; j < DOF; j++) hinv_row[j] = lane < DOF ? row[j] : 0.f;
+        }
     } else if constexpr (COOP) {
         const float* __restrict__ row = coop_area + wave * 64 + 24 + min(lane, DOF - 1) * DOF;
 #pragma unroll
@@ -547,6 +573,28 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
                 const float v = wave_bcast(hinv_col[i], j);  // H^-1(i, j)
                 hinv_row[j] = lane == i ? v : hinv_row[j];
             }
+    }
+    if constexpr (CACHE) {
+        if (cache_fill) {
+            // file the record exactly as the set-up kernel of the split launch shape does (above); a POI that failed the data
+            // part of the guard has come this far for its record alone and now leaves with the reference's code
+            if (lane == 0) {
+                setup_rec[0] = ref_mean;
+                setup_rec[1] = ref_norm;
+            }
+            if constexpr (COOP) {
+                if (lane < DOF * DOF) setup_rec[2 + lane] = coop_area[wave * 64 + 24 + lane];
+            } else {
+                if (lane < DOF) {
+#pragma unroll
+                    for (int i = 0; i < DOF; i++) setup_rec[2 + i * DOF + lane] = hinv_col[i];  // H^-1(i, lane)
+                }
+            }
+            if (guard_data) {
+                if (lane == 0) poi[poi2d::ZNCC] = zncc_in >= 0 ? -3.f : zncc_in;
+                return;
+            }
+        }
     }
 
     lap(1);

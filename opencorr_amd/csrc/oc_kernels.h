@@ -36,6 +36,14 @@ struct Icgn2dParams {
     int arith_fma;  // 1: the build whose per-sample multiply-adds are fused (oc_device.h OC_FMA; oracle OC_ORDER_LANES_FMA)
     float* setup;   // variant 8 (split launch shape): icgn2d_setup_record_floats(dof) floats per POI -- mean, norm, H^-1 -- written by
                     // the set-up kernel and read by the iteration kernel; nullptr otherwise
+    // Set-up cache of the big-queue table variants (4, 5; icgn2d.hip): nullptr = off.  Otherwise icgn2d_setup_record_floats(dof)
+    // floats per POI that outlive the call.  The launch FILLS them (and computes as ever) when cache_force_fill is set or
+    // *cache_word == cache_epoch -- the stamp launch_poi2d_xy_check leaves when the queue's coordinates are not the ones the
+    // records were built for -- and otherwise starts from them.
+    float* cache_recs;
+    const unsigned* cache_word;
+    unsigned cache_epoch;
+    int cache_force_fill;
 };
 // writes max over the queue of (int)subset_radius.x / .y to out2[0], out2[1]
 hipError_t launch_poi2d_max_radius(const float* pois, int stride_floats, size_t count, int* out2, hipStream_t stream);
@@ -99,7 +107,13 @@ int icgn2d_max_samples(int variant);
 // scratch of poi2d_tile_count(height, width, tile_px) unsigned ints, slots = scratch of `count` unsigned ints
 size_t poi2d_tile_count(int height, int width, int tile_px);
 hipError_t launch_poi2d_tile_order(const float* pois, int stride_floats, size_t count, int height, int width, int tile_px,
-                                   unsigned* tiles, unsigned* slots, unsigned* perm, hipStream_t stream);
+                                   unsigned* tiles, unsigned* slots, unsigned* perm, hipStream_t stream, unsigned* xy_copy = nullptr,
+                                   unsigned* xy_word = nullptr, unsigned xy_epoch = 0);
+// Coordinate check of the ICGN2D set-up cache: xy_copy holds the (x, y) bit patterns the records were built for (2 words per
+// POI).  Every POI whose coordinates differ gets its pair rewritten and stamps *word with `epoch` (plain stores of one
+// value).  launch_poi2d_tile_order does the same inside its histogram pass when xy_copy is given: no extra kernel.
+hipError_t launch_poi2d_xy_check(const float* pois, int stride_floats, size_t count, unsigned* xy_copy, unsigned* word, unsigned epoch,
+                                 hipStream_t stream);
 // the same for POI3D queues (cubic tiles of tile_vox voxels): the ICGN3D1 kernels visit the queue block by block
 size_t poi3d_tile_count(int depth, int height, int width, int tile_vox);
 hipError_t launch_poi3d_tile_order(const float* pois, int stride_floats, size_t count, int depth, int height, int width, int tile_vox,

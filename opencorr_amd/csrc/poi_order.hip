@@ -52,11 +52,34 @@ __device__ __forceinline__ int run_of_equal_tiles(unsigned t, bool live, int lan
     return lane - head;
 }
 
+// Set-up cache of ICGN2D (icgn2d.hip): the records were built for the coordinates in xy_copy.  A POI whose x or y bits differ
+// rewrites its pair and stamps the word with this call's epoch, which turns the solver launch behind it into a fill call.
+// Plain vector stores; every writer of the word stores the same value.
+__device__ __forceinline__ void xy_check(const float* poi, unsigned i, unsigned* __restrict__ xy_copy, unsigned* __restrict__ word,
+                                         unsigned epoch) {
+    const unsigned x = __float_as_uint(poi[poi2d::X]), y = __float_as_uint(poi[poi2d::Y]);
+    uint2* slot = reinterpret_cast<uint2*>(xy_copy) + i;
+    const uint2 old = *slot;
+    if (old.x != x || old.y != y) {
+        *slot = make_uint2(x, y);
+        *word = epoch;
+    }
+}
+
+__global__ __launch_bounds__(256) void xy_check_kernel(const float* __restrict__ pois, int stride_f, unsigned count,
+                                                       unsigned* __restrict__ xy_copy, unsigned* __restrict__ word, unsigned epoch) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) xy_check(pois + (size_t)i * stride_f, i, xy_copy, word, epoch);
+}
+
 __global__ __launch_bounds__(256) void tile_histogram_kernel(const float* __restrict__ pois, int stride_f, unsigned count,
                                                              int height, int width, int tile_px, int ntx,
-                                                             unsigned* __restrict__ counts, int depth = 0, int nty = 0) {
+                                                             unsigned* __restrict__ counts, int depth = 0, int nty = 0,
+                                                             unsigned* __restrict__ xy_copy = nullptr, unsigned* __restrict__ xy_word = nullptr,
+                                                             unsigned xy_epoch = 0) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < count;
+    if (xy_copy && live) xy_check(pois + (size_t)i * stride_f, i, xy_copy, xy_word, xy_epoch);
     const unsigned t = live ? tile_of(pois + (size_t)i * stride_f, height, width, tile_px, ntx, depth, nty) : 0u;
     int head, len;
     const int pos = run_of_equal_tiles(t, live, threadIdx.x & 63, head, len);
@@ -139,7 +162,8 @@ size_t poi2d_tile_count(int height, int width, int tile_px) {
 // perm[k] = index of the k-th POI to visit.  `tiles` is scratch for poi2d_tile_count() unsigned ints, `slots` for
 // `count` unsigned ints.
 hipError_t launch_poi2d_tile_order(const float* pois, int stride_f, size_t count, int height, int width, int tile_px,
-                                   unsigned* tiles, unsigned* slots, unsigned* perm, hipStream_t stream) {
+                                   unsigned* tiles, unsigned* slots, unsigned* perm, hipStream_t stream, unsigned* xy_copy,
+                                   unsigned* xy_word, unsigned xy_epoch) {
     if (count == 0) return hipSuccess;
     if (count > 0xffffffffull) return hipErrorInvalidValue;
     const int ntx = (width + tile_px - 1) / tile_px;
@@ -149,7 +173,7 @@ hipError_t launch_poi2d_tile_order(const float* pois, int stride_f, size_t count
     const unsigned blocks = (unsigned)((count + 255) / 256);
     (void)hipGetLastError();
     hipLaunchKernelGGL(tile_histogram_kernel, dim3(blocks), dim3(256), 0, stream, pois, stride_f, (unsigned)count, height, width,
-                       tile_px, ntx, tiles);
+                       tile_px, ntx, tiles, 0, 0, xy_copy, xy_word, xy_epoch);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, stream, tiles, ntiles);
     hipLaunchKernelGGL(tile_scatter_kernel, dim3(blocks), dim3(256), 0, stream, pois, stride_f, (unsigned)count, height, width,
                        tile_px, ntx, tiles, slots);
@@ -158,6 +182,16 @@ hipError_t launch_poi2d_tile_order(const float* pois, int stride_f, size_t count
     const unsigned chunks = (unsigned)(mean4 < 1 ? 1 : (mean4 > (size_t)(kRankCap / 256) ? (size_t)(kRankCap / 256) : mean4));
     hipLaunchKernelGGL(tile_rank_kernel, dim3((unsigned)(ntiles < 65535 ? ntiles : 65535), chunks), dim3(256), 0, stream, ntiles, tiles,
                        slots, perm);
+    return hipGetLastError();
+}
+
+hipError_t launch_poi2d_xy_check(const float* pois, int stride_f, size_t count, unsigned* xy_copy, unsigned* word, unsigned epoch,
+                                 hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    if (count > 0xffffffffull) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(xy_check_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, pois, stride_f, (unsigned)count,
+                       xy_copy, word, epoch);
     return hipGetLastError();
 }
 

@@ -389,6 +389,13 @@ class _IcgnMixin:
         """DIC::setSelfAdaptive (src/oc_dic.cpp:34-37): per-POI subset radius from poi.subset_radius."""
         capi.check(capi.lib().oc_hip_set_self_adaptive(self._h, 1 if is_self_adaptive else 0))
 
+    def setup_cache_last(self):
+        """How the last ICGN2D compute() treated the set-up cache (tuning key "icgn2d_setup_cache"): "none" (went around it),
+        "fill" (computed and filed every POI's set-up) or "use" (started from the filed records).  Waits for the engine."""
+        state = ctypes.c_int()
+        capi.check(capi.lib().oc_hip_icgn2d_setup_cache_last(self._h, ctypes.byref(state)))
+        return {capi.SETUP_CACHE_NONE: "none", capi.SETUP_CACHE_FILL: "fill", capi.SETUP_CACHE_USE: "use"}[state.value]
+
 
 class FFTCC2D(_Engine):
     """FFTCC2D(subset_radius_x, subset_radius_y, thread_number) -- src/oc_fftcc.h:54-68."""
