@@ -313,7 +313,7 @@ int oc_hip_get_devices(const oc_hip_engine* engine, int* device_ids, int capacit
  * synchronised */
 int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** device_ptr, size_t* block_bytes);
 
-/* Knobs.  Every key but "arith_fma" selects among kernels that compute BIT-IDENTICAL results; unknown keys and values
+/* Knobs.  Every key but "arith_fma" and "arith_onepass" selects among kernels that compute BIT-IDENTICAL results; unknown keys and values
  * outside the stated range fail with OC_HIP_ERR_INVALID, values this build does not contain with OC_HIP_ERR_UNSUPPORTED.
  *   "arith_fma"       ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 only (other engines refuse 1).  0 (default): every
  *                     multiply and add of the solver rounds on its own -- the reference built for baseline x86-64; GPU ==
@@ -325,6 +325,25 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     identical iteration counts, |d u, v, w| <= 1e-4 and |d ZNCC| <= 1e-5 (all BASELINE configs:
  *                     tests/test_gpu_fullsize.py).  Kernel time on one MI355X: ICGN2D1 -3 ... -9 %, ICGN2D2 -13 ... -17 %,
  *                     ICGN3D1 -5 ... -7 %.  The once-per-POI dense algebra is never fused
+ *   "arith_onepass"   ICGN2D1 / ICGN2D2 only (every other engine refuses 1 with OC_HIP_ERR_UNSUPPORTED and accepts 0).  0 (default):
+ *                     the contract "arith_fma" selects.  1: the ONE-PASS arithmetic contract (icgn2d_onepass.hip) -- an iteration is
+ *                     one sweep over the warped subset with 3 + DOF running sums of e' = g (t - c) - r~ (c, g: mean and scale of the
+ *                     previous iteration) and no target array; mean, norm, ZNSSD and the numerator are recovered from the sums
+ *                     (DESIGN.md section 3).  The set-up and every per-sample multiply-add are the fused contract's; under 1 the
+ *                     value of "arith_fma" does not matter.  NOT bit-identical to the other two contracts: GPU ==
+ *                     tests/cpp/icgn2d_onepass_twin.cpp (its CPU restatement) bit for bit, and against the reference's separately
+ *                     rounded loop order the same bars as "arith_fma" -- identical failure codes, >= 99.5 % identical iteration
+ *                     counts, |d u, v| <= 1e-4 (whole queues of configs B and C: >= 99.99 % of the POIs, none beyond 2e-4) and
+ *                     |d ZNCC| <= 1e-5; the golden OHT table and the float64 model of ICGN2D2 within their committed bars
+ *                     (tests/test_gpu_arith_onepass.py, tests/test_gpu_fullsize_onepass.py).  Host and device queues, device
+ *                     groups, oc_hip_compute_chain and oc_hip_compute_one work as under the other contracts.  NOT supported under
+ *                     1: centre offsets (oc_hip_compute_with_offsets, oc_hip_compute_one_with_offset) and self-adaptive radii --
+ *                     both fail with OC_HIP_ERR_UNSUPPORTED, they never run another contract -- and the set-up cache, which is
+ *                     simply not used (oc_hip_icgn2d_setup_cache_last reports "none").  Measured compute() time on one MI355X
+ *                     against "arith_fma" = 1 computing its set-up (tools/onepass_ab.py, profiles/r7a_onepass_ab_config_*.json):
+ *                     SLOWER -- ICGN2D1 on config B 3.39 against 3.16 ms (x 1.07), ICGN2D2 on config C 3.66 against 3.17 ms
+ *                     (x 1.15); against "arith_fma" = 1 as it ships, i.e. served by the set-up cache on repeated calls over one
+ *                     reference, x 1.18 and x 1.41.  The contract is an option kept for its arithmetic, not a faster path
  *   "icgn2d_variant"  launch shape of the ICGN2D kernel (gather depth, LDS footprint, per-workgroup coordinate table, waves per
  *                     workgroup); -1 (default) lets the engine choose: 5 / 4 (6 / 12 DoF: coordinate table, lockstep sweeps,
  *                     8-wave workgroups) for queues >= 32768 POIs of subsets up to 35 x 34 / 41 x 41, 2 / 3 (no table) below,

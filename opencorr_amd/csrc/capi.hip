@@ -213,6 +213,15 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     OC_TRY(check_image2d_limits("ICGN2D", im, 1ull << 28));
     const int dof = (e->kind == OC_HIP_ICGN2D1 || e->kind == OC_HIP_ICLM2D1) ? 6 : 12;
     const bool lm = e->is_iclm();
+    // the one-pass arithmetic contract (icgn2d_onepass.hip): one radius per launch, integer local coordinates -- what it does not
+    // support is refused, never run under another contract
+    const bool onepass = e->arith_onepass && !lm;
+    if (onepass && d_offsets)
+        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: centre offsets are not supported under arith_onepass = 1 (the one-pass kernel keeps "
+                                            "integer local coordinates in a per-workgroup table); set arith_onepass = 0 for this call", dof == 6 ? 1 : 2);
+    if (onepass && e->self_adaptive)
+        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: self-adaptive subset radii are not supported under arith_onepass = 1 (the one-pass "
+                                            "kernel runs one radius per launch); set arith_onepass = 0", dof == 6 ? 1 : 2);
     int rx = e->rx, ry = e->ry;
     if (e->self_adaptive) {
         // every POI brings its own radius (src/oc_icgn.cpp:152-158): size the on-chip arrays for the largest
@@ -263,8 +272,12 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     const bool band = false;
 #endif
     if (variant == 9 && !band) variant = dof == 12 ? 3 : 2;
-    if (!band && N > ochip::icgn2d_max_samples(variant)) variant = 1;
-    if (!band && N > ochip::icgn2d_max_samples(variant))
+    if (onepass && N > ochip::icgn2d_onepass_max_samples())
+        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: subset %dx%d (%lld samples) exceeds the one-pass kernel's on-chip limit of %d samples",
+                    dof == 6 ? 1 : 2, 2 * rx + 1, 2 * ry + 1, N, ochip::icgn2d_onepass_max_samples());
+    if (onepass) variant = dof == 6 ? 5 : 4;   // (one launch shape, its own kernel: the variant no longer matters below)
+    if (!band && !onepass && N > ochip::icgn2d_max_samples(variant)) variant = 1;
+    if (!band && !onepass && N > ochip::icgn2d_max_samples(variant))
         return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: subset %dx%d (%lld samples) exceeds the on-chip limit of %d samples",
                     dof == 6 ? 1 : 2, 2 * rx + 1, 2 * ry + 1, N, ochip::icgn2d_max_samples(variant));
     if (variant == 8 && !lm) {
@@ -279,7 +292,7 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     // coordinates the records were built for is decided on the device by the check in front of the launch.  Centre offsets,
     // self-adaptive radii, IC-LM and the small-queue variants go around it.
     e->setup_cache_last = 0;
-    const bool cached = e->icgn2d_setup_cache && !lm && !band && !d_offsets && !e->self_adaptive && (variant == 4 || variant == 5) &&
+    const bool cached = e->icgn2d_setup_cache && !onepass && !lm && !band && !d_offsets && !e->self_adaptive && (variant == 4 || variant == 5) &&
                         count <= kMaxGrid;
     oc_hip_engine::SetupCacheKey cache_key;
     bool cache_hit = false;
@@ -362,7 +375,10 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
             }
             continue;
         }
-        if (lm)
+        if (onepass)
+            err = dof == 6 ? ochip::launch_icgn2d1_onepass(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream)
+                           : ochip::launch_icgn2d2_onepass(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream);
+        else if (lm)
             err = dof == 6 ? ochip::launch_iclm2d1(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream)
                            : ochip::launch_iclm2d2(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream);
 #if OC_BUILD_AB
@@ -804,6 +820,7 @@ static int clone_engine(const oc_hip_engine* e, int device, oc_hip_engine** out)
     r->self_adaptive = e->self_adaptive;
     r->icgn2d_xcd = e->icgn2d_xcd;
     r->arith_fma = e->arith_fma;
+    r->arith_onepass = e->arith_onepass;
     r->icgn2d_split_chunks = e->icgn2d_split_chunks;
     r->icgn2d_setup_cache = e->icgn2d_setup_cache;
     r->fftcc2d_fused = e->fftcc2d_fused;
@@ -1048,6 +1065,10 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
         if (value != 0 && !(e->is_icgn2d() || e->kind == OC_HIP_ICGN3D1))
             return fail(OC_HIP_ERR_UNSUPPORTED, "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines have a fused-arithmetic build");
         e->arith_fma = value != 0;
+    } else if (k == "arith_onepass") {
+        if (value != 0 && !(e->kind == OC_HIP_ICGN2D1 || e->kind == OC_HIP_ICGN2D2))
+            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass: only the ICGN2D1 / ICGN2D2 engines have a one-pass build");
+        e->arith_onepass = value != 0;
     } else if (k == "icgn2d_split_chunks") {
 #if !OC_BUILD_AB
         // (the split launch shape, variant 8, exists in the A/B build only: the key would have no effect here -- ADVICE r5)

@@ -90,6 +90,12 @@ namespace fma {
 hipError_t launch_icgn2d1_band(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 hipError_t launch_icgn2d2_band(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 }
+// icgn2d_onepass.hip: ICGN2D1 / ICGN2D2 under the one-pass arithmetic contract (oc_hip_set_tuning "arith_onepass"): one sweep per
+// iteration, no target array; one radius per launch and no centre offsets (hipErrorNotSupported), hipErrorInvalidValue when the
+// workgroup's coordinate table does not fit LDS.  p.arith_fma does not matter: the kernel is built with the fused multiply-add.
+hipError_t launch_icgn2d1_onepass(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
+hipError_t launch_icgn2d2_onepass(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
+int icgn2d_onepass_max_samples();
 int icgn2d_variant_count();
 int icgn2d_variant_info(int variant, int* g, int* mode, int* pipe, int* wpb, int* occ);
 // variants 0 and 6 are A/B partners that only the A/B build of the library contains (-DOC_BUILD_AB=1)

@@ -158,9 +158,13 @@ class _Engine:
         return ptr.value, blk.value
 
     def set_tuning(self, key, value):
-        """Knob of the C-ABI (``oc_hip_set_tuning``).  Every key but one selects among kernels that compute the same bits;
+        """Knob of the C-ABI (``oc_hip_set_tuning``).  Every key but two selects among kernels that compute the same bits;
         ``"arith_fma"`` = 1 switches the ICGN / IC-LM solvers to the fused arithmetic contract (one rounding fewer per
-        per-sample multiply-add: oracle order ``ORDER_LANES_FMA``; results move by rounding, inside the 1e-4 tolerance)."""
+        per-sample multiply-add: oracle order ``ORDER_LANES_FMA``; results move by rounding, inside the 1e-4 tolerance).
+        ``"arith_onepass"`` = 1 (ICGN2D1 / ICGN2D2 only) selects the one-pass arithmetic contract: an iteration is one sweep with
+        3 + DOF running sums and no target array; bit-exact against ``tests/cpp/icgn2d_onepass_twin.cpp``, same distance bars
+        against the reference's order; ``arith_fma`` does not matter under it.  ``compute_with_offsets`` and
+        ``set_self_adaptive(True)`` raise under it, and the set-up cache is not used."""
         capi.check(capi.lib().oc_hip_set_tuning(self._h, key.encode(), int(value)))
 
     def reset_stream(self):
