@@ -362,6 +362,15 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     the next call rebuild it; the coordinates are compared on the device, no call waits for the host.
  *                     Centre offsets, self-adaptive radii, IC-LM and smaller queues never use it.  0: every call computes its
  *                     set-up.  Same bits either way (oc_hip_icgn2d_setup_cache_last tells which way a call went)
+ *   "icgn2d_int_first"  1 (default): while the warp of an ICGN2D1 / ICGN2D2 POI is an INTEGER TRANSLATION -- integral x, y, u, v and
+ *                     zero gradients: the first iteration of every FFTCC2D guess -- the interpolation sweep reads each sample's
+ *                     value from a value plane that prepare() / prepare_tar() store behind the coefficient table (the
+ *                     interpolant at every pixel's own position, evaluated by the sweep's own polynomial code at zero
+ *                     fractions: 4 B per pixel on top of the table's 64, field "lut_val" of oc_hip_get_field) instead of
+ *                     gathering 16 coefficients and evaluating 15 products with zero.  Every other sweep, centre offsets,
+ *                     self-adaptive radii, IC-LM and the one-pass contract are untouched.  0: every sweep is the full one
+ *                     (the behaviour before the plane existed).  Same bits either way, NaN / Inf pixels included
+ *                     (tests/test_gpu_int_first.py); the key exists for that comparison and for measurements
  *   "icgn2d_split_chunks"  A/B build, variant 8 only: chunks of the two-stream pipeline (0 = the two kernels back to back)
  *   "fftcc2d_fused"   1 (default): single-kernel FFTCC2D (register / LDS FFT) for EVERY window with both radii in 4 ... 32 (even
  *                     sides 8 ... 64): a template instance per square side and for the 42 rectangular pairs (radius_x !=

@@ -240,6 +240,8 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
                              e->self_adaptive ? 1 : 0,
                              lm ? std::log((double)e->lm_lambda) : 0.0,
                              e->lm_alpha,  e->lm_beta,         e->arith_fma,      nullptr};
+    // the value plane behind the target table (oc_hip_prepare_tar): sweeps of integer-translation warps read it ("icgn2d_int_first")
+    P.lut_val = (e->icgn2d_int_first && e->tar_ready && e->coef_has_val) ? e->coef.as<float>() + im.count() * 16 : nullptr;
     const long long N = (2LL * rx + 1) * (2LL * ry + 1);
     // fall back to the LDS-light single-wave variant when the tuned one cannot hold the subset
     int variant = e->icgn2d_variant;
@@ -823,6 +825,7 @@ static int clone_engine(const oc_hip_engine* e, int device, oc_hip_engine** out)
     r->arith_onepass = e->arith_onepass;
     r->icgn2d_split_chunks = e->icgn2d_split_chunks;
     r->icgn2d_setup_cache = e->icgn2d_setup_cache;
+    r->icgn2d_int_first = e->icgn2d_int_first;
     r->fftcc2d_fused = e->fftcc2d_fused;
     r->fftcc3d_fused = e->fftcc3d_fused;
     r->fftcc3d_planes_blocks = e->fftcc3d_planes_blocks;
@@ -857,6 +860,7 @@ static int rehome(oc_hip_engine* e, int device) {
     e->setup_cache_last = 0;
     e->img.reset();
     e->ref_ready = e->tar_ready = false;
+    e->coef_has_val = false;
     e->st_count = 0;
     if (e->order_ev) { (void)hipEventDestroy(e->order_ev); e->order_ev = nullptr; }
     if (e->switch_ev) { (void)hipEventDestroy(e->switch_ev); e->switch_ev = nullptr; }
@@ -1081,6 +1085,10 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
     } else if (k == "icgn2d_setup_cache") {
         // 1 = the big-queue ICGN2D1 / ICGN2D2 launches keep their set-up records from call to call, 0 = every call computes them
         e->icgn2d_setup_cache = value != 0;
+    } else if (k == "icgn2d_int_first") {
+        // 1 = an ICGN2D1 / ICGN2D2 sweep whose warp is an integer translation reads the table's value plane, 0 = every sweep gathers
+        // the coefficients and evaluates the polynomial (the kernel's behaviour before the plane existed; same bits)
+        e->icgn2d_int_first = value != 0;
     } else if (k == "icgn2d_tile_px") {
         if (value < 0 || (value > 0 && value < 16)) return fail(OC_HIP_ERR_INVALID, "icgn2d_tile_px must be 0 (off) or >= 16");
         e->icgn2d_tile_px = value;
@@ -1168,8 +1176,14 @@ int oc_hip_prepare_tar(oc_hip_engine* e) {
     const ImagePair& im = *e->img;
     if (im.ndim == 2) {
         OC_TRY(check_image2d_limits(e->kind == OC_HIP_NR2D1 ? "NR2D1" : "ICGN2D", im, e->kind == OC_HIP_NR2D1 ? 1ull << 26 : 1ull << 28));
-        OC_TRY(e->coef.reserve(im.count() * 16 * sizeof(float)));
-        OC_HIP_TRY(ochip::launch_bspline2d_lut(im.tar_ptr(), im.dy, im.dx, e->coef.as<float>(), e->stream));
+        // ICGN2D1 / ICGN2D2: 17 floats per pixel -- the four coefficient planes and, behind them, the value plane (prepare2d.hip)
+        // in ONE buffer, so that whatever shares, groups or outlives the table does the same for the plane
+        const bool with_val = e->kind == OC_HIP_ICGN2D1 || e->kind == OC_HIP_ICGN2D2;
+        e->coef_has_val = false;
+        OC_TRY(e->coef.reserve(im.count() * (with_val ? 17 : 16) * sizeof(float)));
+        OC_HIP_TRY(ochip::launch_bspline2d_lut(im.tar_ptr(), im.dy, im.dx, e->coef.as<float>(), e->stream,
+                                               with_val ? e->coef.as<float>() + im.count() * 16 : nullptr));
+        e->coef_has_val = with_val;
         if (e->kind == OC_HIP_NR2D1) {
             // gradients of the TARGET and their interpolation tables (src/oc_nr.cpp:121-157)
             OC_TRY(e->gx.reserve(im.count() * sizeof(float)));
@@ -1545,6 +1559,7 @@ int oc_hip_get_field(const oc_hip_engine* e, const char* name, const float** ptr
     else if (s == "gy" && e->ref_ready) { *ptr = e->gy.as<float>(); *count = n; }
     else if (s == "gz" && e->ref_ready && e->is3d()) { *ptr = e->gz.as<float>(); *count = n; }
     else if (s == "lut" && e->tar_ready && !e->is3d()) { *ptr = e->coef.as<float>(); *count = n * 16; }
+    else if (s == "lut_val" && e->tar_ready && !e->is3d() && e->coef_has_val) { *ptr = e->coef.as<float>() + n * 16; *count = n; }
     else if (s == "lut_gx" && e->tar_ready && e->kind == OC_HIP_NR2D1) { *ptr = e->coef_gx.as<float>(); *count = n * 16; }
     else if (s == "lut_gy" && e->tar_ready && e->kind == OC_HIP_NR2D1) { *ptr = e->coef_gy.as<float>(); *count = n * 16; }
     else if (s == "coef" && e->tar_ready && e->is3d()) { *ptr = e->coef.as<float>(); *count = n; }

@@ -206,6 +206,8 @@ struct oc_hip_engine {
     unsigned long long ref_generation = 0;   // bumped by set_images / share_images / prepare_ref: the reference or its gradients changed
     unsigned setup_cache_epoch = 0;          // one per cached launch; the coordinate check stamps the word with it
     int setup_cache_last = 0;                // last run_icgn2d: 0 = went around the cache, 1 = fill (host's decision), 2 = the device word decided
+    int icgn2d_int_first = 1;                // "icgn2d_int_first" tuning key: 0 = every interpolation sweep is the full one (icgn2d.hip kIntSweep)
+    bool coef_has_val = false;               // 2D: the value plane (im.count() floats) lies behind the 16 coefficient floats per pixel in `coef`
     int icgn2d_setup_cache = 1;              // "icgn2d_setup_cache" tuning key: 0 = every call computes its set-up (the behaviour before the cache)
     DevBuf split_scratch, split_tmp; // oc_hip_split_reliable / oc_hip_merge_recovered (poi_split.hip)
     // Strain (src/oc_strain.cpp:31-46: radius, min neighbours; ZNCC threshold 0.9, Cauchy approximation)

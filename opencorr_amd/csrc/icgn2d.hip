@@ -16,7 +16,9 @@
 //     waves re-align, so that neighbouring POIs ask for the same table lines while they are in the CU's L1 -- no data crosses
 //     it; its deadlock-freedom rests on three invariants stated where it is defined);
 //   * the only memory traffic inside the Gauss-Newton loop besides those re-reads is the 64 B / sample gather from the planar
-//     bicubic table (four buffer_load_b128, one per plane) -- the "interpolation sweep".
+//     bicubic table (four buffer_load_b128, one per plane) -- the "interpolation sweep" -- except while the warp is an integer
+//     translation (the first iteration of every FFTCC guess): such a sweep reads 4 B / sample from the table's value plane
+//     and evaluates nothing (`kIntSweep`, tuning key "icgn2d_int_first").
 // Other variants (oc_hip_set_tuning("icgn2d_variant")): 4-wave workgroups without table or barriers for small queues and
 // large subsets (variant 2), one-wave workgroups with everything parked in LDS (variants 0, 1, 3, and the IC-LM engines).
 // Reductions (mean, norms, Hessian, numerator, ZNSSD) are per-lane partial sums in increasing s followed by the xor
@@ -203,6 +205,14 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     //   (b) every wave passes the data-carrying barriers (the table fill, COOP's two) strictly BEFORE its first sweep
     //       barrier, the early leavers through leave() -- so a sweep barrier can only ever pair with sweep barriers;
     //   (c) nothing after the iteration loop waits on a barrier.
+    // Whichever BODY a wave's sweep runs -- the full one (address arithmetic, four gathers, polynomial) or the integer-translation
+    // one (kIntSweep below: one load from the value plane) -- it runs it inside the SAME group loop: the choice is made per pass
+    // group BEHIND the barrier at the loop's head (`short_group` in place of `issue` + `consume`); the loop, its trip count
+    // (NF / G, a property of the launch's subset size) and the barrier are shared.  So every live wave executes the same barrier
+    // sequence per iteration whichever body it runs, and a workgroup may mix the two freely (FFTCC guesses next to user-supplied
+    // or re-solved non-integer ones).  A second loop for the short body would have to restate that trip count and barrier
+    // position to stay correct; there is none on purpose.  (The choice sits at group level and not per sample inside `issue`:
+    // a branch around `issue` alone made the register allocator spill ~100 VGPRs in every instance; this form spills none.)
     // A persistent POI loop, a barrier behind the loop, or a table whose pass count differs between the waves of a workgroup
     // would break one of them (hang, or sweep barriers pairing with COOP's).  kOnePoiPerWave / kBarrierFreeEpilogue state
     // (a) and (c) where such a change would have to flip them; tests/test_gpu_parity_2d.py::
@@ -327,6 +337,11 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     const unsigned goff = (unsigned)__builtin_amdgcn_readfirstlane((((int)py - ry) * width + ((int)px - rx)) * 4);
     const __amdgpu_buffer_rsrc_t r_gx = make_rsrc(P.gx), r_gy = make_rsrc(P.gy), r_ref = make_rsrc(P.ref);
     const LutPlanes4 r_lut(P.lut, height, width);
+    // Integer-translation sweep (ICGN2D1 / ICGN2D2 without centre offsets, every variant of the table below; IC-LM keeps the
+    // full sweep): see the test in front of the sweep.  P.lut_val == nullptr ("icgn2d_int_first" = 0) or self-adaptive radii:
+    // never taken.
+    constexpr bool kIntSweep = LM == 0 && OFFS == 0 && PHASE != 1 && OC_ABLATE2D == 0;
+    const __amdgpu_buffer_rsrc_t r_val = make_rsrc(kIntSweep && P.lut_val ? P.lut_val : P.lut);
     const unsigned w4 = (unsigned)width * 4u;
     // byte offset of sample (r, c) from the subset origin
     auto soff = [&](const SampleWalk& w) { return __umul24((unsigned)w.r, w4) + ((unsigned)w.c << 2); };
@@ -668,6 +683,47 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
                 return;
             }
         }
+        // The sweep of an INTEGER TRANSLATION.  FFTCC2D hands over integral u, v and zero gradients, and POI coordinates are
+        // integral, so in the first iteration of such a POI every sample lands exactly on a pixel: the fractions are zero and the
+        // 16-term polynomial is c00 + 15 products with zero.  prepare() has evaluated exactly that -- lut_value() at dx = dy = 0
+        // on the pixel's coefficients -- into the value plane (prepare2d.hip), so the sweep loads 4 bytes per sample, coalesced
+        // like the numerator pass's reference values, instead of gathering 64.  The test is on the warp this iteration USES, is
+        // wave-uniform, and costs a dozen scalar compares per iteration:
+        //   2D1: W = [1 0 tu; 0 1 tv],  2D2: rows 3, 4 of W = {0 0 0 1 0 tu}, {0 0 0 0 1 tv};  tu, tv, px, py integral, all below 2^22.
+        // Proof that the full sweep would compute the same address and zero fractions (xl, yl: the sample's local coordinates,
+        // small integers, never -0): 1 * xl = xl and 0 * yl = +-0 exactly, fused or not; xl + (+-0) = xl; in 2D2 the chain starts
+        // 0 * xl^2 = +-0 and adds +-0, +-0, 1 * xl, +-0, tu * 1; xl + tu and px + (xl + tu) are sums of integers below 2^23 in
+        // magnitude, hence exact.  So ax = px + tu + xl is an integer >= 1 (range test below): floor(ax) = ax, fract(ax) = +0,
+        // likewise ay, and the sample's pixel is (px + tu - rx + c, py + tv - ry + r): the wave-uniform base below plus the byte
+        // offset the coordinate table (or the sample walk) already holds for the reference image.
+        // `inside` restates the range rule for the subset's rectangle (for 2D1 the corner test above has decided it already; 2D2
+        // tests per sample): a translation that leaves the range takes the full sweep and ends there as it always did, and every
+        // load of the short body is inside the plane.
+        bool int_sweep = false;
+        unsigned val_base = 0;
+        if constexpr (kIntSweep) {
+            if (P.lut_val != nullptr && !P.self_adaptive) {
+                float tu, tv;
+                bool unit;
+                if constexpr (DOF == 6) {
+                    tu = Wm[2];
+                    tv = Wm[5];
+                    unit = Wm[0] == 1.f && Wm[1] == 0.f && Wm[3] == 0.f && Wm[4] == 1.f;
+                } else {
+                    tu = row3[5];
+                    tv = row4[5];
+                    unit = row3[0] == 0.f && row3[1] == 0.f && row3[2] == 0.f && row3[3] == 1.f && row3[4] == 0.f &&
+                           row4[0] == 0.f && row4[1] == 0.f && row4[2] == 0.f && row4[3] == 0.f && row4[4] == 1.f;
+                }
+                constexpr float kExact = 4194304.f;  // 2^22
+                const bool integral = truncf(tu) == tu && truncf(tv) == tv && truncf(px) == px && truncf(py) == py &&
+                                      fabsf(tu) < kExact && fabsf(tv) < kExact && fabsf(px) < kExact && fabsf(py) < kExact;
+                const int x0 = integral ? (int)px + (int)tu - rx : 0, y0 = integral ? (int)py + (int)tv - ry : 0;
+                const bool inside = x0 >= 1 && y0 >= 1 && x0 + 2 * rx <= width - 3 && y0 + 2 * ry <= height - 3;
+                int_sweep = __builtin_amdgcn_readfirstlane((int)(unit && integral && inside)) != 0;
+                val_base = (unsigned)__builtin_amdgcn_readfirstlane(int_sweep ? (y0 * width + x0) * 4 : 0);
+            }
+        }
         {
             SampleWalk w(lane, r0, c0, W, q64, r64);
             constexpr bool kWarpV = (OC_UNIFORM_IN_VGPR & 1) != 0 && DOF == 6, kSizeV = (OC_UNIFORM_IN_VGPR & 2) != 0;
@@ -758,6 +814,34 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
                     }
                 }
             };
+            // the short body of a pass group (int_sweep): the samples' values themselves, from the value plane -- what `issue` +
+            // `consume` leave behind for them (a lane past the end of the subset reads the subset's first pixel; unused)
+            auto short_group = [&](int t0, auto checked) {
+                constexpr bool CHECKED = decltype(checked)::value;
+                float v[G];
+                bool valid[G];
+#pragma unroll
+                for (int g = 0; g < G; g++, w.next()) {
+                    valid[g] = CHECKED ? w.s < N : true;
+                    unsigned off;
+                    if constexpr (TAB) off = off_at(CHECKED ? min(t0 + g, NT - 1) : t0 + g);
+                    else off = soff(w);
+                    if constexpr (CHECKED) off = valid[g] ? off : 0u;
+                    v[g] = buf_f32(r_val, off, val_base);
+                }
+#pragma unroll
+                for (int g = 0; g < G; g++) {
+                    if constexpr (CHECKED) {
+                        negative = negative || (valid[g] && v[g] < 0.f);
+                        acc = valid[g] ? acc + v[g] : acc;
+                        if (t0 + g < NT) l_ts[(t0 + g) * kWave] = v[g];
+                    } else {
+                        negative = negative || v[g] < 0.f;
+                        acc = acc + v[g];
+                        l_ts[(t0 + g) * kWave] = v[g];
+                    }
+                }
+            };
             // groups of G passes in which every lane owns a sample need no validity logic
             const int full_groups = NF / G;
             int t0 = 0;
@@ -765,6 +849,13 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
             for (int q = 0; q < full_groups; q++, t0 += G) {
                 if constexpr (SWEEP_SYNC > 0) {
                     if (q % SWEEP_SYNC == 0) __builtin_amdgcn_s_barrier();
+                }
+                if constexpr (kIntSweep) {
+                    // (the body is chosen BEHIND the barrier, inside the one loop: see the invariants at the top)
+                    if (int_sweep) {
+                        short_group(t0, std::false_type{});
+                        continue;
+                    }
                 }
 #if OC_ABLATE2D & 4
                 LutFetch(&f)[G] = f_stale;
@@ -790,6 +881,12 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
 #endif
 #pragma nounroll
             for (; t0 < NT; t0 += G) {
+                if constexpr (kIntSweep) {
+                    if (int_sweep) {
+                        short_group(t0, std::true_type{});
+                        continue;
+                    }
+                }
 #if OC_ABLATE2D & 4
                 LutFetch(&f)[G] = f_stale;
 #else

@@ -15,7 +15,9 @@ namespace ochip {
 
 // ---- prepare2d.hip ---------------------------------------------------------
 hipError_t launch_grad2d(const float* img, int height, int width, float* gx, float* gy, hipStream_t stream);
-hipError_t launch_bspline2d_lut(const float* img, int height, int width, float* lut, hipStream_t stream);
+// value_plane (optional, height * width floats): the table's interpolant at each pixel's own integer position -- lut_value() of
+// the pixel's 16 coefficients at dx = dy = 0 -- for the integer-translation sweep of icgn2d.hip (Icgn2dParams::lut_val)
+hipError_t launch_bspline2d_lut(const float* img, int height, int width, float* lut, hipStream_t stream, float* value_plane = nullptr);
 hipError_t launch_colmajor_to_rowmajor(const float* src, int height, int width, float* dst, hipStream_t stream);
 
 // ---- icgn2d.hip ------------------------------------------------------------
@@ -44,6 +46,10 @@ struct Icgn2dParams {
     const unsigned* cache_word;
     unsigned cache_epoch;
     int cache_force_fill;
+    // Value plane of the target table (launch_bspline2d_lut), or nullptr: the interpolation sweep of a wave whose warp is an integer
+    // translation reads a sample's value from it instead of gathering the 16 coefficients (icgn2d.hip, kIntSweep); nullptr = every
+    // sweep is the full one ("icgn2d_int_first" = 0)
+    const float* lut_val;
 };
 // writes max over the queue of (int)subset_radius.x / .y to out2[0], out2[1]
 hipError_t launch_poi2d_max_radius(const float* pois, int stride_floats, size_t count, int* out2, hipStream_t stream);

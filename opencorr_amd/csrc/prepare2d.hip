@@ -5,8 +5,8 @@
 //   colmajor_to_rowmajor Eigen::MatrixXf (column-major, src/oc_image.h:37) -> x-fastest
 //
 // All three are HBM streaming kernels: one thread per pixel, 4 B read (neighbours
-// come from L1/L2), 8 B (gradients) or 64 B (LUT: 4 planes x 16 B) written per pixel.
-#include "oc_device.h"
+// come from L1/L2), 8 B (gradients) or 64 B (LUT: 4 planes x 16 B; + 4 B with the value plane) written per pixel.
+#include "dic2d_device.h"
 #include "oc_kernels.h"
 
 namespace ochip {
@@ -57,8 +57,21 @@ __device__ constexpr float kBC[4][4] = {
 // the reference, src/oc_array.h:92).  The table is stored PLANAR (dic2d_device.h): plane k holds the float4
 // coef[k][0..3] of every pixel, row-major -- a wave's store is 1 KiB of consecutive bytes per plane, and the
 // solvers' gathers touch a quarter of the cache lines an interleaved 64-byte entry cost them.
+//
+// VALUE PLANE (`val`, optional: the target table of ICGN2D1 / ICGN2D2): what the solvers' interpolation computes for a sample
+// that lands exactly on this pixel -- lut_value() (dic2d_device.h, the one definition the sweeps call) on the 16 coefficients
+// held here, with dx = dy = 0.  A sweep whose warp is an integer translation loads this float instead of gathering the
+// coefficients and evaluating the polynomial (icgn2d.hip, kIntSweep).  Same bits as that evaluation BY CONSTRUCTION, whatever
+// the pixels are: the chain is c00 + c01 * 0 + ... + ((c33 * 0) * 0), every product an IEEE operation on the same operands --
+// (+-)0 for a finite coefficient, NaN for an infinite or NaN one -- and every addition the same left-to-right chain; nothing
+// depends on the data being finite, so no flag travels with the plane.  ONE plane serves both arithmetic modes: the fused
+// form replaces "w + round(c * 0)" by "fma(c, 0, w)", and since c * 0 is exact (a signed zero) or NaN, rounding it first
+// changes nothing -- both give w + (+-0), or NaN; the inner products ((c * 0) * 0) are formed unfused in both modes.  (The
+// zeros are hidden from the compiler below so that it emits the sweep's own instruction sequence instead of folding.)
+// For a finite neighbourhood the value is the pixel itself (last row of kBC: {0, 1, 0, 0}), with -0 turned into +0 by the
+// sum that starts from +0; reading the image instead would be wrong exactly where the pixels are not finite.
 __global__ __launch_bounds__(256) void bspline2d_lut_kernel(const float* __restrict__ img, int height, int width,
-                                                            float* __restrict__ lut) {
+                                                            float* __restrict__ lut, float* __restrict__ val) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int r = blockIdx.y;
     if (c >= width) return;
@@ -67,6 +80,7 @@ __global__ __launch_bounds__(256) void bspline2d_lut_kernel(const float* __restr
     if (r < 1 || r >= height - 2 || c < 1 || c >= width - 2) {
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         out[0] = z; out[plane] = z; out[2 * plane] = z; out[3 * plane] = z;
+        if (val) val[(size_t)r * width + c] = 0.f;  // (the polynomial of sixteen zeros)
         return;
     }
     float q[4][4];
@@ -88,6 +102,16 @@ __global__ __launch_bounds__(256) void bspline2d_lut_kernel(const float* __restr
         }
 #pragma unroll
     for (int k = 0; k < 4; k++) out[k * plane] = make_float4(pm[3 - k][3], pm[3 - k][2], pm[3 - k][1], pm[3 - k][0]);
+    if (val) {
+        LutFetch f;
+        f.c0 = make_float4(pm[3][3], pm[3][2], pm[3][1], pm[3][0]);
+        f.c1 = make_float4(pm[2][3], pm[2][2], pm[2][1], pm[2][0]);
+        f.c2 = make_float4(pm[1][3], pm[1][2], pm[1][1], pm[1][0]);
+        f.c3 = make_float4(pm[0][3], pm[0][2], pm[0][1], pm[0][0]);
+        f.dx = in_vgpr(0.f);
+        f.dy = in_vgpr(0.f);
+        val[(size_t)r * width + c] = lut_value(f);
+    }
 }
 
 // dst[r*width + c] = src[c*height + r]; LDS-tiled so both sides stay coalesced.
@@ -177,10 +201,10 @@ hipError_t launch_grad2d(const float* img, int height, int width, float* gx, flo
     return hipGetLastError();
 }
 
-hipError_t launch_bspline2d_lut(const float* img, int height, int width, float* lut, hipStream_t stream) {
+hipError_t launch_bspline2d_lut(const float* img, int height, int width, float* lut, hipStream_t stream, float* value_plane) {
     dim3 block(256), grid((width + 255) / 256, height);
     (void)hipGetLastError();  // drop stale errors of earlier, unrelated calls
-    hipLaunchKernelGGL(bspline2d_lut_kernel, grid, block, 0, stream, img, height, width, lut);
+    hipLaunchKernelGGL(bspline2d_lut_kernel, grid, block, 0, stream, img, height, width, lut, value_plane);
     return hipGetLastError();
 }
 
