@@ -10,7 +10,8 @@
 // the device is chosen with the extra setters setDevice() / setDevices() or the OC_HIP_DEVICE / OC_HIP_DEVICES
 // environment variables (OC_HIP_DEVICES=all: every engine spreads its queues over all GPUs of the node; OC_HIP_ARITH_FMA=1: the
 // ICGN / IC-LM solvers run under the fused arithmetic contract, see oc_hip_set_tuning "arith_fma"; OC_HIP_ARITH_ONEPASS=1: ICGN2D1 / ICGN2D2
-// run under the one-pass arithmetic contract, "arith_onepass" -- their centre-offset overloads and setSelfAdaptive(true) then throw).  Failures of the engine (no GPU, bad call order, ...)
+// run under the one-pass arithmetic contract, "arith_onepass" -- their centre-offset overloads and setSelfAdaptive(true) then throw;
+// OC_HIP_ARITH_ONEPASS3D=1: ICGN3D1 runs under its one-pass arithmetic contract, "arith_onepass3d").  Failures of the engine (no GPU, bad call order, ...)
 // are thrown as std::string like the reference does (src/oc_fftcc.cpp:145, src/oc_icgn.cpp:65).
 //
 // Differences a caller can observe (documented):
@@ -134,6 +135,13 @@ inline bool arithOnepassFromEnvironment() {
     return op && std::atoi(op) != 0;
 }
 
+// true when OC_HIP_ARITH_ONEPASS3D switches the ICGN3D1 engines created through these classes to their one-pass contract
+// (OC_HIP_ARITH_ONEPASS keeps meaning the 2D engines only)
+inline bool arithOnepass3dFromEnvironment() {
+    const char* op = std::getenv("OC_HIP_ARITH_ONEPASS3D");
+    return op && std::atoi(op) != 0;
+}
+
 inline void apply_default_devices(oc_hip_engine* e) {
     const std::vector<int> ids = default_devices();
     if (ids.size() > 1) check(oc_hip_set_devices(e, ids.data(), (int)ids.size()));
@@ -168,6 +176,20 @@ inline void apply_default_devices(oc_hip_engine* e) {
                 std::fprintf(stderr, "opencorr_hip: OC_HIP_ARITH_ONEPASS=1 -- the ICGN2D1 / ICGN2D2 solvers of this process use the one-pass arithmetic "
                                      "contract (one sweep per iteration; results differ from the default build by rounding, inside 1e-4 px; "
                                      "centre offsets and self-adaptive radii are refused).  OC_HIP_QUIET=1 silences this note.\n");
+        }
+    }
+    // OC_HIP_ARITH_ONEPASS3D=1: ICGN3D1 uses its one-pass arithmetic contract (oc_hip_set_tuning "arith_onepass3d",
+    // include/opencorr_hip.h); every other engine is left alone
+    if (arithOnepass3dFromEnvironment()) {
+        int kind = 0;
+        if (oc_hip_get_kind(e, &kind) == OC_HIP_OK && kind == OC_HIP_ICGN3D1) {
+            check(oc_hip_set_tuning(e, "arith_onepass3d", 1));
+            static std::atomic<bool> said_onepass3d{false};
+            const char* quiet = std::getenv("OC_HIP_QUIET");
+            if (!(quiet && *quiet && *quiet != '0') && !said_onepass3d.exchange(true))
+                std::fprintf(stderr, "opencorr_hip: OC_HIP_ARITH_ONEPASS3D=1 -- the ICGN3D1 solvers of this process use the one-pass arithmetic "
+                                     "contract (one sweep per iteration, no stored samples; results differ from the default build by "
+                                     "rounding, inside 1e-4 voxel).  OC_HIP_QUIET=1 silences this note.\n");
         }
     }
 }

@@ -313,7 +313,7 @@ int oc_hip_get_devices(const oc_hip_engine* engine, int* device_ids, int capacit
  * synchronised */
 int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** device_ptr, size_t* block_bytes);
 
-/* Knobs.  Every key but "arith_fma" and "arith_onepass" selects among kernels that compute BIT-IDENTICAL results; unknown keys and values
+/* Knobs.  Every key but "arith_fma", "arith_onepass" and "arith_onepass3d" selects among kernels that compute BIT-IDENTICAL results; unknown keys and values
  * outside the stated range fail with OC_HIP_ERR_INVALID, values this build does not contain with OC_HIP_ERR_UNSUPPORTED.
  *   "arith_fma"       ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 only (other engines refuse 1).  0 (default): every
  *                     multiply and add of the solver rounds on its own -- the reference built for baseline x86-64; GPU ==
@@ -344,6 +344,21 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     SLOWER -- ICGN2D1 on config B 3.39 against 3.16 ms (x 1.07), ICGN2D2 on config C 3.66 against 3.17 ms
  *                     (x 1.15); against "arith_fma" = 1 as it ships, i.e. served by the set-up cache on repeated calls over one
  *                     reference, x 1.18 and x 1.41.  The contract is an option kept for its arithmetic, not a faster path
+ *   "arith_onepass3d" ICGN3D1 only (every other engine refuses 1 with OC_HIP_ERR_UNSUPPORTED and accepts 0; ICGN3D1 in turn refuses
+ *                     "arith_onepass" = 1 and names this key).  0 (default): the contract "arith_fma" selects.  1: the ONE-PASS
+ *                     arithmetic contract carried to DVC (icgn3d_onepass.hip) -- the tap sweep of an iteration forms, per sample,
+ *                     e' = g (t - c) - r~ and adds it to 3 + 12 running sums; no warped sample is stored, no scratch is reserved,
+ *                     and mean, norm, ZNSSD and the numerator are recovered from the sums after ONE block reduction (DESIGN.md
+ *                     section 3).  The set-up and every per-sample multiply-add are the fused contract's; under 1 the value of
+ *                     "arith_fma" does not matter.  NOT bit-identical to the other two contracts: GPU ==
+ *                     tests/cpp/icgn3d_onepass_twin.cpp (its CPU restatement, 512-lane association) bit for bit, and against the
+ *                     reference's separately rounded loop order the same bars as "arith_fma" -- identical failure codes,
+ *                     >= 99.5 % identical iteration counts, |d u, v, w| <= 1e-4 and |d ZNCC| <= 1e-5; the float64 model of the
+ *                     3D iteration within its committed bars (tests/test_onepass3d_twin_cpu.py,
+ *                     tests/test_gpu_arith_onepass3d.py).  Host and device queues, device groups, oc_hip_compute_chain,
+ *                     oc_hip_compute_one and "icgn3d_tile_vox" work as under the other contracts; the A/B build's
+ *                     "icgn3d_mapping" = 1 together with this key fails with OC_HIP_ERR_UNSUPPORTED.  NOT RUN ON AN MI355X YET:
+ *                     neither the kernel's bits nor its time have been measured (tools/onepass3d_ab.py)
  *   "icgn2d_variant"  launch shape of the ICGN2D kernel (gather depth, LDS footprint, per-workgroup coordinate table, waves per
  *                     workgroup); -1 (default) lets the engine choose: 5 / 4 (6 / 12 DoF: coordinate table, lockstep sweeps,
  *                     8-wave workgroups) for queues >= 32768 POIs of subsets up to 35 x 34 / 41 x 41, 2 / 3 (no table) below,

@@ -539,6 +539,12 @@ int run_icgn3d1(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
     const ImagePair& im = *e->img;
     int blocks = 0;
     size_t scratch = ochip::icgn3d1_scratch_floats(e->rx, e->ry, e->rz, &blocks);
+    // the one-pass arithmetic contract (icgn3d_onepass.hip) stores no sample: no scratch.  It has one mapping; a call that asks for
+    // the other one is refused, never run under another contract
+    const bool onepass = e->arith_onepass3d != 0;
+    if (onepass && e->icgn3d_mapping != 0)
+        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN3D1: the row mapping (icgn3d_mapping = 1) has no one-pass build (arith_onepass3d = 1)");
+    if (onepass) scratch = 0;
 #if OC_BUILD_AB
     // the row mapping (icgn3d_rows.hip, an A/B partner: only the A/B build contains it) keeps whole steps per thread: its
     // slots are a little larger
@@ -556,10 +562,12 @@ int run_icgn3d1(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
     OC_TRY(tile_order3d(e, d_pois, stride_f, count, e->icgn3d_tile_vox, &P.perm));
     ProfScope prof(e);
 #if OC_BUILD_AB
-    hipError_t err = e->icgn3d_mapping != 0 ? ochip::launch_icgn3d1_rows(P, d_pois, stride_f, count, blocks, e->stream)
-                                            : ochip::launch_icgn3d1(P, d_pois, stride_f, count, e->stream);
+    hipError_t err = onepass                  ? ochip::launch_icgn3d1_onepass(P, d_pois, stride_f, count, e->stream)
+                     : e->icgn3d_mapping != 0 ? ochip::launch_icgn3d1_rows(P, d_pois, stride_f, count, blocks, e->stream)
+                                              : ochip::launch_icgn3d1(P, d_pois, stride_f, count, e->stream);
 #else
-    hipError_t err = ochip::launch_icgn3d1(P, d_pois, stride_f, count, e->stream);
+    hipError_t err = onepass ? ochip::launch_icgn3d1_onepass(P, d_pois, stride_f, count, e->stream)
+                             : ochip::launch_icgn3d1(P, d_pois, stride_f, count, e->stream);
 #endif
     if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "ICGN3D1 kernel launch failed: %s", hipGetErrorString(err));
     return OC_HIP_OK;
@@ -823,6 +831,7 @@ static int clone_engine(const oc_hip_engine* e, int device, oc_hip_engine** out)
     r->icgn2d_xcd = e->icgn2d_xcd;
     r->arith_fma = e->arith_fma;
     r->arith_onepass = e->arith_onepass;
+    r->arith_onepass3d = e->arith_onepass3d;
     r->icgn2d_split_chunks = e->icgn2d_split_chunks;
     r->icgn2d_setup_cache = e->icgn2d_setup_cache;
     r->icgn2d_int_first = e->icgn2d_int_first;
@@ -1070,9 +1079,17 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
             return fail(OC_HIP_ERR_UNSUPPORTED, "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines have a fused-arithmetic build");
         e->arith_fma = value != 0;
     } else if (k == "arith_onepass") {
+        if (value != 0 && e->kind == OC_HIP_ICGN3D1)
+            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass: the key of the ICGN2D1 / ICGN2D2 engines; the one-pass build of ICGN3D1 has a "
+                                                "key of its own, arith_onepass3d");
         if (value != 0 && !(e->kind == OC_HIP_ICGN2D1 || e->kind == OC_HIP_ICGN2D2))
             return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass: only the ICGN2D1 / ICGN2D2 engines have a one-pass build");
         e->arith_onepass = value != 0;
+    } else if (k == "arith_onepass3d") {
+        if (value != 0 && e->kind != OC_HIP_ICGN3D1)
+            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass3d: only the ICGN3D1 engine has this one-pass build (ICGN2D1 / ICGN2D2: "
+                                                "arith_onepass)");
+        e->arith_onepass3d = value != 0;
     } else if (k == "icgn2d_split_chunks") {
 #if !OC_BUILD_AB
         // (the split launch shape, variant 8, exists in the A/B build only: the key would have no effect here -- ADVICE r5)

@@ -242,6 +242,7 @@ struct oc_hip_engine {
     // tolerance: DESIGN.md section 3)
     int arith_fma = 0;
     int arith_onepass = 0;       // "arith_onepass" tuning key (ICGN2D1 / ICGN2D2): the one-pass arithmetic contract, icgn2d_onepass.hip
+    int arith_onepass3d = 0;     // "arith_onepass3d" tuning key (ICGN3D1): the one-pass arithmetic contract, icgn3d_onepass.hip
     int fftcc2d_fused = 1;    // single-kernel FFTCC2D when the window is 32 x 32
     int fftcc3d_fused = 1;    // single-kernel FFTCC3D for cubic windows of side 8 ... 64 (three kernels by size)
     int fftcc3d_planes_blocks = 0;  // persistent workgroups (= scratch volumes) of the plane-wise kernel; 0 = 256

@@ -248,6 +248,10 @@ hipError_t launch_icgn3d1(const Icgn3dParams& p, float* pois, int stride_floats,
 namespace fma {
 hipError_t launch_icgn3d1(const Icgn3dParams& p, float* pois, int stride_floats, size_t count, hipStream_t stream);
 }
+// icgn3d_onepass.hip: ICGN3D1 under the one-pass arithmetic contract (oc_hip_set_tuning "arith_onepass3d"): the tap sweep forms
+// 15 running sums and stores no sample, one block reduction per iteration.  Mapping and launch shape of launch_icgn3d1; p.scratch is
+// not read and p.arith_fma does not matter: the kernel is built with the fused multiply-add.
+hipError_t launch_icgn3d1_onepass(const Icgn3dParams& p, float* pois, int stride_floats, size_t count, hipStream_t stream);
 // icgn3d_rows.hip (A/B builds only, OC_BUILD_AB; NOT the default -- the default is icgn3d.hip, oracle order OC_ORDER_LANES): the
 // same solver with one half-wave per subvolume row (oracle order OC_ORDER_ROWS), measured 12 - 25 % slower; its scratch
 // slots are a little larger (whole steps): icgn3d1_rows_slot_floats floats per workgroup, 512 workgroups

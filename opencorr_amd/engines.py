@@ -164,7 +164,10 @@ class _Engine:
         ``"arith_onepass"`` = 1 (ICGN2D1 / ICGN2D2 only) selects the one-pass arithmetic contract: an iteration is one sweep with
         3 + DOF running sums and no target array; bit-exact against ``tests/cpp/icgn2d_onepass_twin.cpp``, same distance bars
         against the reference's order; ``arith_fma`` does not matter under it.  ``compute_with_offsets`` and
-        ``set_self_adaptive(True)`` raise under it, and the set-up cache is not used."""
+        ``set_self_adaptive(True)`` raise under it, and the set-up cache is not used.
+        ``"arith_onepass3d"`` = 1 (ICGN3D1 only) is the same contract for DVC: the tap sweep forms 15 running sums, no warped
+        sample is stored and no scratch is reserved; bit-exact against ``tests/cpp/icgn3d_onepass_twin.cpp``; ``arith_fma`` does
+        not matter under it.  ICGN3D1 refuses ``"arith_onepass"`` and names this key."""
         capi.check(capi.lib().oc_hip_set_tuning(self._h, key.encode(), int(value)))
 
     def reset_stream(self):

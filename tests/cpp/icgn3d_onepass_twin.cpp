@@ -1,0 +1,369 @@
+// icgn3d_onepass_twin.cpp -- CPU restatement of the one-pass arithmetic contract of ICGN3D1
+// (oc_hip_set_tuning "arith_onepass3d", opencorr_amd/csrc/icgn3d_onepass.hip).
+//
+// Test infrastructure: the kernel must equal this file in EVERY bit.  Built by tests/onepass3d_twin.py with
+// g++ -O2 -ffp-contract=off -fopenmp: the compiler contracts nothing, every fused site is an explicit std::fmaf, every
+// other operation rounds on its own.  Arrays are those of oracle.Prepared3D (reference volume, its three gradients, the
+// tricubic coefficient volume of the target), records are POI3D (31 floats).
+//
+// Summation: sample s = (i * SY + j) * SX + k is owned by lane s % 512, a lane adds its samples in increasing s, the 512
+// partial sums are combined by the xor butterfly with ascending offsets 1, 2, ... 256 -- the butterfly inside each wave of
+// 64 and then the balanced tree over the 8 wave sums in wave order, the association of block_allreduce in icgn3d_device.h.
+// A lane without a sample contributes exact +0.
+//
+// Set-up per POI, four sweeps over the subvolume:
+//   1  mean r- = (sum r) / N                                       (what the fused contract computes)
+//   2  r~ = r - r-;  R2 = sum fma(r~, r~),  R0 = sum r~,  A_j = sum SD_j,  B_j = sum fma(SD_j, r~);  |R| = sqrt(R2)
+//      (a sweep of its own: R2 is the fused contract's, the 25 constants R0, A_j, B_j are new; the kernel takes the 26 sums as
+//      two half sweeps of 14 and 12)
+//   3, 4  H = sum fma(SD_i, SD_j), H^-1 by LU with partial pivoting
+// (the kernel also splits the 78 sums of H over two sweeps; every sum is one lane-ordered sum, so no split changes a bit)
+// with SD = g_x (1, x, y, z), g_y (1, x, y, z), g_z (1, x, y, z), each product rounded once.
+// Iteration: ONE sweep.  With the carried shift c (first: r-) and scale g (first: 1) a sample contributes
+// e' = fma(g, t - c, -r~) to  E0 += e',  E2 = fma(e', e', E2),  Er = fma(e', r~, Er),  E_j = fma(SD_j, e', E_j);  the scalar
+// expressions behind the reduction are written out in scalars() below, each operation rounded on its own.  Everything
+// behind b -- dp = H^-1 b, the 4 x 4 warp update, the norm, the exits, which fields are written -- is the default path's.
+#include <cmath>
+#include <cstddef>
+#include <vector>
+
+namespace {
+
+constexpr int kLanes = 512;
+
+template <int K>
+struct Acc {
+    std::vector<float> part;   // [K][512]
+    Acc() : part((size_t)K * kLanes, 0.f) {}
+    inline void add(int s, int k, float v) { part[(size_t)k * kLanes + (s & (kLanes - 1))] += v; }
+    inline void mac(int s, int k, float x, float y) {
+        float& slot = part[(size_t)k * kLanes + (s & (kLanes - 1))];
+        slot = std::fmaf(x, y, slot);
+    }
+    inline void finish() {
+        float tmp[kLanes];
+        for (int k = 0; k < K; k++) {
+            float* p = &part[(size_t)k * kLanes];
+            for (int off = 1; off < kLanes; off <<= 1) {
+                for (int l = 0; l < kLanes; l++) tmp[l] = p[l] + p[l ^ off];
+                for (int l = 0; l < kLanes; l++) p[l] = tmp[l];
+            }
+        }
+    }
+    inline float get(int k) const { return part[(size_t)k * kLanes]; }
+};
+
+// inverse of the 12 x 12 row-major Hessian: LU with partial (row) pivoting, solve against the identity
+void lu_inverse12(const float* A, float* Ainv) {
+    constexpr int n = 12;
+    float lu[n * n];
+    int perm[n];
+    for (int i = 0; i < n * n; i++) lu[i] = A[i];
+    for (int i = 0; i < n; i++) perm[i] = i;
+    for (int k = 0; k < n; k++) {
+        int piv = k;
+        float best = std::fabs(lu[k * n + k]);
+        for (int r = k + 1; r < n; r++) {
+            const float v = std::fabs(lu[r * n + k]);
+            if (v > best) { best = v; piv = r; }
+        }
+        if (piv != k) {
+            for (int c = 0; c < n; c++) { const float t = lu[k * n + c]; lu[k * n + c] = lu[piv * n + c]; lu[piv * n + c] = t; }
+            const int t = perm[k]; perm[k] = perm[piv]; perm[piv] = t;
+        }
+        const float d = lu[k * n + k];
+        for (int r = k + 1; r < n; r++) {
+            const float f = lu[r * n + k] / d;
+            lu[r * n + k] = f;
+            for (int c = k + 1; c < n; c++) lu[r * n + c] = lu[r * n + c] - f * lu[k * n + c];
+        }
+    }
+    for (int col = 0; col < n; col++) {
+        float y[n];
+        for (int i = 0; i < n; i++) {
+            float v = (perm[i] == col) ? 1.f : 0.f;
+            for (int j = 0; j < i; j++) v = v - lu[i * n + j] * y[j];
+            y[i] = v;
+        }
+        for (int i = n - 1; i >= 0; i--) {
+            float v = y[i];
+            for (int j = i + 1; j < n; j++) v = v - lu[i * n + j] * y[j];
+            y[i] = v / lu[i * n + i];
+        }
+        for (int i = 0; i < n; i++) Ainv[i * n + col] = y[i];
+    }
+}
+
+inline float det3(float a, float b, float c, float d, float e, float f, float g, float h, float i) {
+    return (a * (e * i - f * h) - b * (d * i - f * g)) + c * (d * h - e * g);
+}
+// 4 x 4 inverse by cofactor expansion
+void inverse4(const float* m, float* r) {
+    float cofm[16];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            float s[9];
+            int t = 0;
+            for (int a = 0; a < 4; a++) {
+                if (a == i) continue;
+                for (int b = 0; b < 4; b++) {
+                    if (b == j) continue;
+                    s[t++] = m[a * 4 + b];
+                }
+            }
+            const float d = det3(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8]);
+            cofm[i * 4 + j] = ((i + j) & 1) ? -d : d;
+        }
+    const float det = ((m[0] * cofm[0] + m[1] * cofm[1]) + m[2] * cofm[2]) + m[3] * cofm[3];
+    const float invdet = 1.f / det;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) r[i * 4 + j] = cofm[j * 4 + i] * invdet;
+}
+
+inline void set_warp(float* w, const float* q) {
+    w[0] = 1.f + q[1]; w[1] = q[2]; w[2] = q[3]; w[3] = q[0];
+    w[4] = q[5]; w[5] = 1.f + q[6]; w[6] = q[7]; w[7] = q[4];
+    w[8] = q[9]; w[9] = q[10]; w[10] = 1.f + q[11]; w[11] = q[8];
+    w[12] = 0.f; w[13] = 0.f; w[14] = 0.f; w[15] = 1.f;
+}
+
+// cubic B-spline weights, every Horner step "product + constant" fused
+inline float basis0(float t) { return (1.f / 6.f) * std::fmaf(t, std::fmaf(t, -t + 3.f, -3.f), 1.f); }
+inline float basis1(float t) { return (1.f / 6.f) * std::fmaf(t * t, std::fmaf(3.f, t, -6.f), 4.f); }
+inline float basis2(float t) { return (1.f / 6.f) * std::fmaf(t, std::fmaf(t, std::fmaf(-3.f, t, 3.f), 3.f), 1.f); }
+inline float basis3(float t) { return (1.f / 6.f) * (t * t * t); }
+// one product, three fused multiply-adds
+inline float taps4(const float* b, float r0, float r1, float r2, float r3) {
+    return std::fmaf(b[3], r3, std::fmaf(b[2], r2, std::fmaf(b[1], r1, b[0] * r0)));
+}
+
+// tricubic value; -1 outside the interpolatable range
+inline float bspline3d(const float* coef, int dz, int dy, int dx, float x, float y, float z) {
+    if (x < 1 || y < 1 || z < 1 || x >= dx - 2 || y >= dy - 2 || z >= dz - 2 || std::isnan(x) || std::isnan(y) || std::isnan(z))
+        return -1.f;
+    const int xi = (int)std::floor(x), yi = (int)std::floor(y), zi = (int)std::floor(z);
+    const float fx = x - xi, fy = y - yi, fz = z - zi;
+    const float bx[4] = {basis0(fx), basis1(fx), basis2(fx), basis3(fx)};
+    const float by[4] = {basis0(fy), basis1(fy), basis2(fy), basis3(fy)};
+    const float bz[4] = {basis0(fz), basis1(fz), basis2(fz), basis3(fz)};
+    float sum_y[4];
+    for (int i = 0; i < 4; i++) {
+        float sum_x[4];
+        for (int j = 0; j < 4; j++) {
+            const float* row = coef + ((size_t)(zi + i - 1) * dy + (yi + j - 1)) * dx + (xi - 1);
+            sum_x[j] = taps4(bx, row[0], row[1], row[2], row[3]);
+        }
+        sum_y[i] = taps4(by, sum_x[0], sum_x[1], sum_x[2], sum_x[3]);
+    }
+    return taps4(bz, sum_y[0], sum_y[1], sum_y[2], sum_y[3]);
+}
+
+inline void sd_row(float g_x, float g_y, float g_z, float xl, float yl, float zl, float* sd) {
+    sd[0] = g_x; sd[1] = g_x * xl; sd[2] = g_x * yl; sd[3] = g_x * zl;
+    sd[4] = g_y; sd[5] = g_y * xl; sd[6] = g_y * yl; sd[7] = g_y * zl;
+    sd[8] = g_z; sd[9] = g_z * xl; sd[10] = g_z * yl; sd[11] = g_z * zl;
+}
+
+// What follows the reduction of an iteration's sums: every operation rounds on its own, in exactly this order.
+struct Scalars {
+    float m, f, znssd, alpha, a, q;
+};
+inline Scalars scalars(float E0, float E2, float Er, float R0, float R2, float ref_norm, float fN, float g) {
+    Scalars r;
+    const float S1 = (E0 + R0) / g;
+    const float S2 = ((E2 + 2.f * Er) + R2) / (g * g);
+    r.m = S1 / fN;
+    const float tar_norm = std::sqrt(S2 - S1 * r.m);
+    r.f = ref_norm / tar_norm;
+    r.a = (r.f - g) / g;
+    r.alpha = 1.f + r.a;
+    r.q = r.f * r.m;
+    float z = (r.alpha * r.alpha) * E2;
+    z = z + (r.a * r.a) * R2;
+    z = z + (fN * r.q) * r.q;
+    z = z + ((2.f * r.alpha) * r.a) * Er;
+    z = z - ((2.f * r.alpha) * r.q) * E0;
+    z = z - ((2.f * r.a) * r.q) * R0;
+    r.znssd = z / R2;
+    return r;
+}
+
+struct Images3D {
+    const float *ref, *gx, *gy, *gz, *coef;
+    int dz, dy, dx;
+};
+
+void onepass_poi(const Images3D& im, int rx, int ry, int rz, float conv, float stop, float* poi, std::vector<float>& scratch) {
+    const float px = poi[0], py = poi[1], pz = poi[2];
+    float* p = poi + 3;      // u ux uy uz v vx vy vz w wx wy wz
+    float* res = poi + 15;   // u0 v0 w0 zncc iteration convergence
+    float* srad = poi + 28;
+    const int DX = im.dx, DY = im.dy, DZ = im.dz;
+    if ((px - rx) < 0 || (py - ry) < 0 || (pz - rz) < 0 || (px + rx) > (DX - 1) || (py + ry) > (DY - 1) || (pz + rz) > (DZ - 1) ||
+        std::fabs(p[0]) >= DX || std::fabs(p[4]) >= DY || std::fabs(p[8]) >= DZ || res[3] < 0 || std::isnan(p[0]) ||
+        std::isnan(p[4]) || std::isnan(p[8])) {
+        res[3] = res[3] >= 0 ? -3.f : res[3];
+        return;
+    }
+    const int SX = 2 * rx + 1, SY = 2 * ry + 1, SZ = 2 * rz + 1;
+    const int N = SX * SY * SZ;
+    const float fN = (float)N;
+    scratch.resize((size_t)N * 4);
+    float* rs = scratch.data();
+    float* sgx = rs + N;
+    float* sgy = sgx + N;
+    float* sgz = sgy + N;
+
+    // ---- set-up
+    float ref_mean, ref_norm, R0, R2;
+    {
+        // the reference subvolume: float additions truncated per element (Subset3D::fill)
+        const float sx = px - rx, sy = py - ry, sz = pz - rz;
+        Acc<1> a;
+        int s = 0;
+        for (int i = 0; i < SZ; i++)
+            for (int j = 0; j < SY; j++)
+                for (int k = 0; k < SX; k++, s++) {
+                    rs[s] = im.ref[((size_t)(int)(sz + i) * DY + (int)(sy + j)) * DX + (int)(sx + k)];
+                    a.add(s, 0, rs[s]);
+                }
+        a.finish();
+        ref_mean = a.get(0) / fN;
+    }
+    float A[12], B[12], hess[144], hinv[144];
+    {
+        Acc<26> aux;   // R2, R0, A_j, B_j
+        Acc<78> ah;
+        const int cx = (int)px, cy = (int)py, cz = (int)pz;
+        int s = 0;
+        for (int i = 0; i < SZ; i++)
+            for (int j = 0; j < SY; j++)
+                for (int k = 0; k < SX; k++, s++) {
+                    const int xl = k - rx, yl = j - ry, zl = i - rz;
+                    const size_t g = ((size_t)(cz + zl) * DY + (cy + yl)) * DX + (cx + xl);
+                    sgx[s] = im.gx[g]; sgy[s] = im.gy[g]; sgz[s] = im.gz[g];
+                    const float d = rs[s] - ref_mean;
+                    rs[s] = d;
+                    float sd[12];
+                    sd_row(sgx[s], sgy[s], sgz[s], (float)xl, (float)yl, (float)zl, sd);
+                    aux.mac(s, 0, d, d);
+                    aux.add(s, 1, d);
+                    for (int q = 0; q < 12; q++) {
+                        aux.add(s, 2 + q, sd[q]);
+                        aux.mac(s, 14 + q, sd[q], d);
+                    }
+                    int t = 0;
+                    for (int r = 0; r < 12; r++)
+                        for (int c = 0; c <= r; c++) ah.mac(s, t++, sd[r], sd[c]);
+                }
+        aux.finish();
+        ah.finish();
+        R2 = aux.get(0);
+        R0 = aux.get(1);
+        ref_norm = std::sqrt(R2);
+        for (int q = 0; q < 12; q++) {
+            A[q] = aux.get(2 + q);
+            B[q] = aux.get(14 + q);
+        }
+        int t = 0;
+        for (int r = 0; r < 12; r++)
+            for (int c = 0; c <= r; c++) {
+                hess[r * 12 + c] = ah.get(t);
+                hess[c * 12 + r] = ah.get(t);
+                t++;
+            }
+    }
+    lu_inverse12(hess, hinv);
+
+    float init[12];
+    for (int i = 0; i < 12; i++) init[i] = p[i];
+    float Wm[16];
+    set_warp(Wm, init);
+    float cur[12];
+    int iter = 0;
+    float dp_norm = 0.f, znssd = 0.f;
+    float cshift = ref_mean, gscale = 1.f;
+    do {
+        iter++;
+        bool negative = false;
+        Acc<15> ae;   // E_0..11, E0, E2, Er
+        int s = 0;
+        for (int i = 0; i < SZ; i++)
+            for (int j = 0; j < SY; j++)
+                for (int k = 0; k < SX; k++, s++) {
+                    const float xl = (float)(k - rx), yl = (float)(j - ry), zl = (float)(i - rz);
+                    const float wx = std::fmaf(Wm[2], zl, std::fmaf(Wm[1], yl, Wm[0] * xl)) + Wm[3] * 1.f;
+                    const float wy = std::fmaf(Wm[6], zl, std::fmaf(Wm[5], yl, Wm[4] * xl)) + Wm[7] * 1.f;
+                    const float wz = std::fmaf(Wm[10], zl, std::fmaf(Wm[9], yl, Wm[8] * xl)) + Wm[11] * 1.f;
+                    const float t = bspline3d(im.coef, DZ, DY, DX, px + wx, py + wy, pz + wz);
+                    if (t < 0.f) negative = true;
+                    const float e = std::fmaf(gscale, t - cshift, -rs[s]);
+                    float sd[12];
+                    sd_row(sgx[s], sgy[s], sgz[s], xl, yl, zl, sd);
+                    for (int q = 0; q < 12; q++) ae.mac(s, q, sd[q], e);
+                    ae.add(s, 12, e);
+                    ae.mac(s, 13, e, e);
+                    ae.mac(s, 14, e, rs[s]);
+                }
+        if (negative) {
+            res[3] = -3.f;
+            return;
+        }
+        ae.finish();
+        const Scalars sc = scalars(ae.get(12), ae.get(13), ae.get(14), R0, R2, ref_norm, fN, gscale);
+        znssd = sc.znssd;
+        float num[12];
+        for (int q = 0; q < 12; q++) num[q] = (sc.alpha * ae.get(q) + sc.a * B[q]) - sc.q * A[q];
+        cshift = cshift + sc.m;
+        gscale = sc.f;
+
+        float dp[12];
+        for (int i = 0; i < 12; i++) {
+            float v = 0.f;
+            for (int j = 0; j < 12; j++) v += hinv[i * 12 + j] * num[j];
+            dp[i] = v;
+        }
+        float dW[16], dWi[16], Wn[16];
+        set_warp(dW, dp);
+        inverse4(dW, dWi);
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++) {
+                float v = Wm[i * 4 + 0] * dWi[0 * 4 + j];
+                for (int k = 1; k < 4; k++) v = v + Wm[i * 4 + k] * dWi[k * 4 + j];
+                Wn[i * 4 + j] = v;
+            }
+        for (int i = 0; i < 16; i++) Wm[i] = Wn[i];
+        cur[0] = Wm[3]; cur[1] = Wm[0] - 1.f; cur[2] = Wm[1]; cur[3] = Wm[2];
+        cur[4] = Wm[7]; cur[5] = Wm[4]; cur[6] = Wm[5] - 1.f; cur[7] = Wm[6];
+        cur[8] = Wm[11]; cur[9] = Wm[8]; cur[10] = Wm[9]; cur[11] = Wm[10] - 1.f;
+        dp_norm = std::sqrt(dp[0] * dp[0] + dp[4] * dp[4] + dp[8] * dp[8]);
+    } while (iter < stop && dp_norm >= conv);
+
+    for (int i = 0; i < 12; i++) p[i] = cur[i];
+    res[0] = init[0];
+    res[1] = init[4];
+    res[2] = init[8];
+    res[3] = 0.5f * (2 - znssd);
+    res[4] = (float)iter;
+    res[5] = dp_norm;
+    srad[0] = (float)rx; srad[1] = (float)ry; srad[2] = (float)rz;
+    if (res[5] >= conv && res[4] >= stop) res[3] = -4.f;
+    if (std::isnan(res[3]) || std::isnan(p[0]) || std::isnan(p[4]) || std::isnan(p[8])) {
+        p[0] = res[0]; p[4] = res[1]; p[8] = res[2];
+        res[3] = -5.f;
+    }
+}
+
+}  // namespace
+
+extern "C" void oc_twin_icgn3d_onepass(const float* ref, const float* gx, const float* gy, const float* gz, const float* coef, int dz,
+                                       int dy, int dx, int rx, int ry, int rz, float conv, float stop, float* pois, long n,
+                                       int stride_floats) {
+    const Images3D im = {ref, gx, gy, gz, coef, dz, dy, dx};
+#pragma omp parallel
+    {
+        std::vector<float> scratch;
+#pragma omp for schedule(dynamic, 1)
+        for (long i = 0; i < n; i++) onepass_poi(im, rx, ry, rz, conv, stop, pois + (size_t)i * stride_floats, scratch);
+    }
+}
