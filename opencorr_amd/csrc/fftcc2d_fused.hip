@@ -370,6 +370,11 @@ __global__ __launch_bounds__(64 * kX2Waves, OC_FFTCC2D_X2_OCC) void fftcc2d_fuse
         if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
     }
     if (l == 0) {
+        // a constant window: the reference's all-zero surface (oc_device.h, "Constant windows in the fused FFTCC kernels")
+        if (rn == 0.f || tn == 0.f) {
+            best = 0.f;
+            bidx = 0;
+        }
         int du = bidx % FN, dv = bidx / FN;
         if (du > rx) du -= FN;
         if (dv > ry) dv -= FN;

@@ -194,6 +194,11 @@ __global__ __launch_bounds__(64 * kFusedNWaves) void fftcc2d_fusedn_kernel(Fftcc
     }
     if (l == 0) {
         if (bidx == 0x7fffffff) bidx = 0;
+        // a constant window: the reference's all-zero surface (oc_device.h, "Constant windows in the fused FFTCC kernels")
+        if (rn == 0.f || tn == 0.f) {
+            best = 0.f;
+            bidx = 0;
+        }
         // the peak is decoded with the WINDOW's width (src/oc_fftcc.cpp:257-266), whatever shape the transform had
         int du = bidx % NR, dv = bidx / NR;
         if (du > rx) du -= NR;

@@ -265,6 +265,11 @@ __global__ __launch_bounds__(kBoxMaxThreads) void fftcc3d_box_kernel(Fftcc3dPara
                 best = red[i];
                 bidx = redi[i];
             }
+        // a constant window: the reference's all-zero surface (oc_device.h, "Constant windows in the fused FFTCC kernels")
+        if (rn == 0.f || tn == 0.f) {
+            best = 0.f;
+            bidx = 0;
+        }
         int du = bidx % nx, dv = (bidx / nx) % ny, dw = bidx / (nx * ny);  // src/oc_fftcc.cpp:401-403: decoded as a WINDOW position
         if (du > P.rx) du -= nx;
         if (dv > P.ry) dv -= ny;

@@ -329,6 +329,16 @@ __device__ __forceinline__ void fftcc3d_fused32_poi(const Fftcc3dParams& P, floa
                 best = red[i];
                 bidx = redi[i];
             }
+        // a constant window: the reference's all-zero surface (oc_device.h, "Constant windows in the fused FFTCC kernels")
+        float rn = 0.f, tn = 0.f;
+        for (int i = 0; i < kWaves; i++) {
+            rn += red2[i];
+            tn += red2[kWaves + i];
+        }
+        if (rn == 0.f || tn == 0.f) {
+            best = 0.f;
+            bidx = 0;
+        }
         int du = bidx % TN, dv = (bidx / TN) % TN, dw = bidx / (TN * TN);  // src/oc_fftcc.cpp:401-403
         if (du > R) du -= TN;
         if (dv > R) dv -= TN;
@@ -340,11 +350,6 @@ __device__ __forceinline__ void fftcc3d_fused32_poi(const Fftcc3dParams& P, floa
         poi[poi3d::U0] = gu;
         poi[poi3d::V0] = gv;
         poi[poi3d::W0] = gw;
-        float rn = 0.f, tn = 0.f;
-        for (int i = 0; i < kWaves; i++) {
-            rn += red2[i];
-            tn += red2[kWaves + i];
-        }
         poi[poi3d::ZNCC] = (0.25f * best) / (sqrtf(rn * tn) * M);
     }
 }

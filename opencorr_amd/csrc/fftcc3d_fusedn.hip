@@ -263,6 +263,11 @@ __global__ __launch_bounds__(Cube<N>::BLOCK) void fftcc3d_fusedn_kernel(Fftcc3dP
                 best = red[i];
                 bidx = redi[i];
             }
+        // a constant window: the reference's all-zero surface (oc_device.h, "Constant windows in the fused FFTCC kernels")
+        if (rn == 0.f || tn == 0.f) {
+            best = 0.f;
+            bidx = 0;
+        }
         int du = bidx % N, dv = (bidx / N) % N, dw = bidx / (N * N);  // src/oc_fftcc.cpp:401-403
         if (du > R) du -= N;
         if (dv > R) dv -= N;

@@ -335,6 +335,11 @@ __global__ __launch_bounds__(kPlThreads) void fftcc3d_planes_kernel(Fftcc3dParam
                     bidx = redi[i];
                 }
             if (bidx == 0x7fffffff) bidx = 0;  // nothing above -2 (a NaN volume): the reference keeps index 0
+            // a constant window: the reference's all-zero surface (oc_device.h, "Constant windows in the fused FFTCC kernels")
+            if (rn == 0.f || tn == 0.f) {
+                best = 0.f;
+                bidx = 0;
+            }
             int du = bidx % N, dv = (bidx / N) % N, dw = bidx / (N * N);  // src/oc_fftcc.cpp:401-403
             if (du > R) du -= N;
             if (dv > R) dv -= N;

@@ -20,6 +20,15 @@
 //                       GPU == oracle stays exact; the per-POI dense algebra is NOT fused in either mode.
 // Helpers whose bodies depend on OC_FMA are __device__ __forceinline__ only (no symbol is ever emitted for them, and
 // every translation unit is its own device code object), and the kernels built from them live in ochip::sep / ochip::fma.
+//
+// Constant windows in the fused FFTCC kernels: a window of constant intensity is identically zero once its mean is removed, and
+// its norm is exactly 0.  The reference transforms the two windows separately: the spectrum of zeros is zeros, the surface is
+// exactly zero, the strict '>' scan keeps index 0 and ZNCC is 0 / 0.  The fused kernels split ONE transform of ref + i*tar, which
+// leaves rounding residue of the other window instead, whose arg-max is no peak.  So every epilogue tests `rn == 0 || tn == 0` and
+// keeps the reference's zeros (peak 0 at index 0).  The oracle tests "every zero-mean sample == 0" instead; the two agree unless
+// the squares of a non-constant window all underflow (subnormal-scale images, which nothing here supports yet).  The two A/B
+// partners that the product library never launches (fftcc2d_fused32_kernel, fftcc3d_fused_r5.hip) do not have the branch: no
+// test reaches them with a constant window.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -454,6 +454,19 @@ static void xcorr_nd(const float* ref, const float* tar, const std::vector<int>&
     for (int d : dims) total *= d;
     buf.resize(total);
     spec.resize(total);
+    // A window of constant intensity is identically zero once its mean is removed.  The reference transforms the two windows
+    // separately: the spectrum of zeros is zeros, so is the product, so is the surface -- exactly, and the strict '>' scan then
+    // keeps index 0.  Separating two spectra out of ONE transform of ref + i*tar leaves rounding residue of the other window
+    // instead (1e-16 of its energy), whose arg-max is anywhere: keep the reference's zeros.
+    bool ref_zero = true, tar_zero = true;
+    for (size_t i = 0; i < total; i++) {
+        ref_zero = ref_zero && ref[i] == 0.f;
+        tar_zero = tar_zero && tar[i] == 0.f;
+    }
+    if (ref_zero || tar_zero) {
+        for (size_t i = 0; i < total; i++) surface[i] = 0.f;
+        return;
+    }
     for (size_t i = 0; i < total; i++) buf[i] = cplx((double)ref[i], (double)tar[i]);
     fft_nd(buf, dims, -1, cache);
     // index of -k
