@@ -391,7 +391,10 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     sides 8 ... 64): a template instance per square side and for the 42 rectangular pairs (radius_x !=
  *                     radius_y) out of sides 16, 20, 24, 32, 40, 48, 64, one kernel with run-time sides (fftcc2d_rect.hip) for
  *                     every other rectangular pair; larger windows run the rocFFT pipeline.  0: rocFFT pipeline always.  2: as
- *                     1, but 32 x 32 windows run the generic NR x NC kernel instead of their own (an A/B switch)
+ *                     1, but 32 x 32 windows run the generic NR x NC kernel instead of their own (an A/B switch).  3: as 1, but
+ *                     the 32 x 32 kernel runs its body without the scalar row stepping of integral POIs and with a full complex
+ *                     last inverse pass (the kernel before those two changes); 4 / 5: with the first / the second of the two
+ *                     alone (A/B switches: same integers, ZNCC of 3 and 4 bit-identical)
  *   "fftcc3d_fused"   1 (default): single-kernel FFTCC3D for every cubic window of even side 8 ... 64 (radius 4 ... 32): LDS kernel
  *                     up to 26^3, register kernel at 32^3, plane-wise kernel for 28^3 ... 64^3; and for every NON-cubic window
  *                     with all three radii in 4 ... 16 whose complex volume [2rx][2ry][2rz + 1] fits 160 KB of LDS (one kernel,

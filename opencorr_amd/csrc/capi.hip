@@ -123,7 +123,7 @@ int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
         for (size_t first = 0; first < count; first += kMaxBatch) {
             const size_t n = (count - first) < kMaxBatch ? (count - first) : kMaxBatch;
             float* q = d_pois + first * (size_t)stride_f;
-            hipError_t err = fused32 ? ochip::launch_fftcc2d_fused(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream)
+            hipError_t err = fused32 ? ochip::launch_fftcc2d_fused(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream, e->fftcc2d_fused)
                              : rect  ? ochip::launch_fftcc2d_rect(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream)
                                      : ochip::launch_fftcc2d_fusedn(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream);
             if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "fused FFTCC2D launch failed: %s", hipGetErrorString(err));
@@ -1110,7 +1110,9 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
         if (value < 0 || (value > 0 && value < 16)) return fail(OC_HIP_ERR_INVALID, "icgn2d_tile_px must be 0 (off) or >= 16");
         e->icgn2d_tile_px = value;
     } else if (k == "fftcc2d_fused") {
-        e->fftcc2d_fused = value == 2 ? 2 : (value != 0);
+        // 3 = the 32 x 32 kernel's body without the fast row stepping and the real-output last pass, 4 / 5 = with the first /
+        // the second of them alone (A/B partners; every other window shape treats 3 ... 5 like 1)
+        e->fftcc2d_fused = (value >= 2 && value <= 5) ? value : (value != 0);
     } else if (k == "fftcc3d_fused") {
 #if !OC_BUILD_AB
         if (value == 2)

@@ -388,5 +388,29 @@ OC_FFT_FN void fft_mixed(c2 (&v)[N]) {
     fft_mixed_at<INV, N, N, 0, N>(v);
 }
 
+// Inverse 32-point transform of a HERMITIAN line with real output: x[n] = sum_k X[k] exp(+2 pi i k n / 32), X[32 - k] =
+// conj X[k], from X[0 .. 16] alone (the imaginary parts of X[0] and X[16], zero for an exactly Hermitian line, are not
+// read).  The even and the odd samples are the real and the imaginary part of one 16-point transform:
+//   x[2m] + i x[2m+1] = sum_(k<16) Z[k] exp(2 pi i k m / 16),   Z[k] = (X[k] + conj X[16-k]) + i W^-k (X[k] - conj X[16-k]),
+// W = exp(-2 pi i / 32).  Z[k] and Z[16-k] share their sum S and their twiddled difference T: Z[k] = S + iT, Z[16-k] =
+// conj(S - iT).  17 + 32 butterflies' worth of arithmetic against the 80 of fft32.  On return x[2m] = z[fft_pos(16, m)].x,
+// x[2m+1] = z[fft_pos(16, m)].y.
+template <int LEN>
+OC_FFT_FN void ifft32_hermitian(const c2 (&X)[LEN], c2 (&z)[16]) {
+    static_assert(LEN >= 17, "needs X[0 .. 16]");
+    z[0] = mkc(X[0].x + X[16].x, X[0].x - X[16].x);
+    z[8] = mkc(X[8].x + X[8].x, -(X[8].y + X[8].y));
+    static_for<1, 8>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        constexpr float tc = Twiddle<32>::c[k], ts = Twiddle<32>::s[k];
+        const c2 p = X[k], q = mkc(X[16 - k].x, -X[16 - k].y);
+        const c2 s = p + q;
+        const c2 t = cmul_tw<true>(p - q, tc, ts);
+        z[k] = mkc(s.x - t.y, s.y + t.x);
+        z[16 - k] = mkc(s.x + t.y, t.x - s.y);
+    });
+    fft_mixed_at<true, 16, 16, 0, 16>(z);
+}
+
 }  // namespace fftdev
 }  // namespace ochip

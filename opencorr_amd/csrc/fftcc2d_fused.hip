@@ -207,6 +207,18 @@ __global__ __launch_bounds__(64 * kFusedWaves) void fftcc2d_fused32_kernel(Fftcc
 // (line, half) mapping 0.70 - 0.72 ms (16 / 19 / 32 resident waves per CU alike); this mapping with c2 tiles (9 waves per CU)
 // 0.60 ms; with the tile split into a real and an imaginary round (OC_FFTCC2D_X2_SPLIT: half the LDS per POI, 16 waves per
 // CU, 120 VGPRs) 0.54 ms.  1 140 VALU (458 of them packed) and 110 LDS wave-instructions per POI against 1 412 / 140.
+// Two template parameters carry the gfx950 instruction-count work on this body; <false, false> is the round-3
+// kernel instruction for instruction, and tuning "fftcc2d_fused" = 3 / 4 / 5 launches <false, false> / <true, false> / <false, true>:
+//   * FAST_ROWS: a wave whose live lanes all hold integral x, y, u, v fetches row k from the lane's byte offset of row 0 plus the
+//     scalar offset k * pitch -- the 258 VALU instructions between the first and the last window load (one float add chain, two
+//     conversions, a 24-bit multiply and an add-shift per row and image) become 0 VALU and 37 scalar ones; any fractional value in
+//     the wave keeps the per-row expressions.  No bit of any record moves.
+//   * REAL_LAST: the last inverse pass reads only rows 0 .. 16 of the Hermitian array back from the tile and runs the real-output
+//     transform ifft32_hermitian (fft_device.h) instead of a complex fft32: 77 VALU and 14 LDS instructions fewer (the compiler
+//     had already dropped the imaginary halves of the complex pass's last stage).  ZNCC moves in its last bits, integers do not.
+// Static counts per wave (hipcc -O3, product flags; every v_* / v_pk_* / ds_* / buffer_load opcode): <false, false> 2 160 VALU,
+// 915 of them packed, 221 LDS, 64 loads, 120 VGPRs; <true, true> on its fast path 1 815 / 917 / 207 / 64 (on the slow path
+// 2 095; 128 loads and 2 103 VALU in the text), 120 VGPRs; 0 B of scratch in all four instances.
 #ifndef OC_FFTCC2D_X2_WAVES
 #define OC_FFTCC2D_X2_WAVES 1
 #endif
@@ -224,6 +236,7 @@ __device__ __forceinline__ float half_wave_sum(float v) {
     return v;
 }
 
+template <bool FAST_ROWS, bool REAL_LAST>
 __global__ __launch_bounds__(64 * kX2Waves, OC_FFTCC2D_X2_OCC) void fftcc2d_fused32x2_kernel(Fftcc2dParams P, float* __restrict__ pois, int stride_f,
                                                                          unsigned long long count, int xcd_chunk) {
     __shared__ c2 lds[kX2Waves * 2 * FWAVE_LDS / (OC_FFTCC2D_X2_SPLIT ? 2 : 1)];
@@ -251,12 +264,27 @@ __global__ __launch_bounds__(64 * kX2Waves, OC_FFTCC2D_X2_OCC) void fftcc2d_fuse
     {
         const __amdgpu_buffer_rsrc_t r_ref = make_rsrc(P.ref), r_tar = make_rsrc(P.tar);
         const float rxp = px + l - rx, txp = rxp + gu;
+        // Integral px, py, gu, gv (every benchmark POI: a grid, zero guesses) make each float sum below exact -- the guard has
+        // bounded them inside the image, far below 2^24 -- so (int)(py + k - ry) = (int)(py - ry) + k and the target row
+        // likewise: row k is the lane's offset of row 0 plus the wave-uniform k * pitch, which the load takes as its scalar
+        // offset (both POIs of a wave share the pitch).  One ballot over the lanes that passed the guard decides for the
+        // wave; a wave with any fractional value keeps the per-row expressions, whose truncations are reference behaviour.
+        const bool integral = px == (float)(int)px && py == (float)(int)py && gu == (float)(int)gu && gv == (float)(int)gv;
+        if (FAST_ROWS && __builtin_amdgcn_ballot_w64(!integral) == 0) {
+            const float ry0 = py - ry, ty0 = ry0 + gv;
+            const unsigned ref0 = (__umul24((unsigned)(int)ry0, (unsigned)width) + (unsigned)(int)rxp) << 2;
+            const unsigned tar0 = (__umul24((unsigned)(int)ty0, (unsigned)width) + (unsigned)(int)txp) << 2;
+            const unsigned pitch = (unsigned)width << 2;
 #pragma unroll
-        for (int k = 0; k < FN; k++) {
-            const float ryp = py + k - ry, typ = ryp + gv;
-            const float a = buf_f32(r_ref, (__umul24((unsigned)(int)ryp, (unsigned)width) + (unsigned)(int)rxp) << 2, 0);
-            const float b = buf_f32(r_tar, (__umul24((unsigned)(int)typ, (unsigned)width) + (unsigned)(int)txp) << 2, 0);
-            v[k] = mkc(a, b);
+            for (int k = 0; k < FN; k++) v[k] = mkc(buf_f32(r_ref, ref0, k * pitch), buf_f32(r_tar, tar0, k * pitch));
+        } else {
+#pragma unroll
+            for (int k = 0; k < FN; k++) {
+                const float ryp = py + k - ry, typ = ryp + gv;
+                const float a = buf_f32(r_ref, (__umul24((unsigned)(int)ryp, (unsigned)width) + (unsigned)(int)rxp) << 2, 0);
+                const float b = buf_f32(r_tar, (__umul24((unsigned)(int)typ, (unsigned)width) + (unsigned)(int)txp) << 2, 0);
+                v[k] = mkc(a, b);
+            }
         }
         float rsum = 0.f, tsum = 0.f;
 #pragma unroll
@@ -348,21 +376,54 @@ __global__ __launch_bounds__(64 * kX2Waves, OC_FFTCC2D_X2_OCC) void fftcc2d_fuse
     fft32<true>(u);
 #pragma unroll
     for (int k = 0; k < FN; k++) v[k] = u[k];
-    OC_X2_TRANSPOSE(l * FP + k, k * FP + l)
-#undef OC_X2_TRANSPOSE
-#pragma unroll
-    for (int k = 0; k < FN; k++) u[k] = v[k];
-    fft32<true>(u);  // u[bitrev5(r)] = correlation surface (row r, column l)
-
-    // ---- arg-max with "strict >, scanning from index 0" (src/oc_fftcc.cpp:246-255): the lane's 32 values sit at linear
-    // indices r * 32 + l, ascending in r; then the half-wave's 32 columns, the lower index winning a tie
+    // arg-max with "strict >, scanning from index 0" (src/oc_fftcc.cpp:246-255): the lane's 32 values sit at linear indices
+    // r * 32 + l, ascending in r; then the half-wave's 32 columns, the lower index winning a tie
     float best = -2.f;
     int bidx = 0;
+    if constexpr (REAL_LAST) {
+        // D(32 - kr, x) = conj D(kr, x) (the product is exactly Hermitian, the first inverse pass keeps it to rounding) and
+        // only the real part of the surface is read: the pass along kr is a real-output transform of rows kr = 0 .. 16
+        // (fft_device.h ifft32_hermitian: a 16-point complex transform behind the half-length recombination).  Rows
+        // 17 .. 31 are written to the tile (their lanes run the same instructions anyway) but never read back.
+#if OC_FFTCC2D_X2_SPLIT
 #pragma unroll
-    for (int r = 0; r < FN; r++) {
-        const float val = u[bitrev5(r)].x;
-        if (val > best) { best = val; bidx = r * FN + l; }
+        for (int k = 0; k < FN; k++) ft[l * FP + k] = v[bitrev5(k)].x;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k <= FN / 2; k++) v[k].x = ft[k * FP + l];
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < FN; k++) ft[l * FP + k] = v[bitrev5(k)].y;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k <= FN / 2; k++) v[k].y = ft[k * FP + l];
+#else
+#pragma unroll
+        for (int k = 0; k < FN; k++) tile[l * FP + k] = v[bitrev5(k)];
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k <= FN / 2; k++) v[k] = tile[k * FP + l];
+#endif
+        c2 z[FN / 2];
+        ifft32_hermitian(v, z);  // surface rows 2m, 2m + 1 of column l = z[fft_pos(16, m)].x, .y
+        static_for<0, FN>([&](auto rc) {
+            constexpr int r = decltype(rc)::value;
+            constexpr int pos = fft_pos(FN / 2, r >> 1);  // (a constant expression: a run-time fft_pos() costs scalar code)
+            const float val = (r & 1) ? z[pos].y : z[pos].x;
+            if (val > best) { best = val; bidx = r * FN + l; }
+        });
+    } else {
+        OC_X2_TRANSPOSE(l * FP + k, k * FP + l)
+#pragma unroll
+        for (int k = 0; k < FN; k++) u[k] = v[k];
+        fft32<true>(u);  // u[bitrev5(r)] = correlation surface (row r, column l)
+#pragma unroll
+        for (int r = 0; r < FN; r++) {
+            const float val = u[bitrev5(r)].x;
+            if (val > best) { best = val; bidx = r * FN + l; }
+        }
     }
+#undef OC_X2_TRANSPOSE
 #pragma unroll
     for (int off = 1; off < 32; off <<= 1) {
         const float ov = __shfl_xor(best, off, kWave);
@@ -389,7 +450,7 @@ __global__ __launch_bounds__(64 * kX2Waves, OC_FFTCC2D_X2_OCC) void fftcc2d_fuse
 bool fftcc2d_fused_supported(int rx, int ry) { return rx == FN / 2 && ry == FN / 2; }
 
 hipError_t launch_fftcc2d_fused(const Fftcc2dParams& p, float* pois, int stride_f, size_t count, bool xcd,
-                                hipStream_t stream) {
+                                hipStream_t stream, int body) {
     if (count == 0) return hipSuccess;
     if (!fftcc2d_fused_supported(p.rx, p.ry)) return hipErrorInvalidValue;
     (void)hipGetLastError();  // drop stale errors of earlier, unrelated calls
@@ -398,7 +459,13 @@ hipError_t launch_fftcc2d_fused(const Fftcc2dParams& p, float* pois, int stride_
         const size_t groups = (count + 2 * kX2Waves - 1) / (2 * kX2Waves);
         const int chunk = xcd ? (int)((groups + 7) / 8) : 0;
         const size_t grid = xcd ? (size_t)chunk * 8 : groups;
-        hipLaunchKernelGGL(fftcc2d_fused32x2_kernel, dim3((unsigned)grid), dim3(64 * kX2Waves), 0, stream, p, pois, stride_f,
+        // body: 3 = the kernel as it was before the fast row stepping and the real-output last pass, 4 / 5 = one of the two
+        // alone (A/B partners: tuning key "fftcc2d_fused"); anything else = both
+        auto kern = body == 3 ? fftcc2d_fused32x2_kernel<false, false>
+                    : body == 4 ? fftcc2d_fused32x2_kernel<true, false>
+                    : body == 5 ? fftcc2d_fused32x2_kernel<false, true>
+                                : fftcc2d_fused32x2_kernel<true, true>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * kX2Waves), 0, stream, p, pois, stride_f,
                            (unsigned long long)count, chunk);
         return hipGetLastError();
     }

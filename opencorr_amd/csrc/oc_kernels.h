@@ -291,8 +291,9 @@ hipError_t launch_fftcc2d_rect(const Fftcc2dParams& p, float* pois, int stride_f
 // ---- fftcc2d_fused.hip -----------------------------------------------------
 // whole FFTCC2D::compute for 32 x 32 windows (rx == ry == 16) in one kernel, no rocFFT, no scratch
 bool fftcc2d_fused_supported(int rx, int ry);
+// body: 3 / 4 / 5 = the A/B partners of the gfx950 instruction-count work (fftcc2d_fused.hip), anything else = the default
 hipError_t launch_fftcc2d_fused(const Fftcc2dParams& p, float* pois, int stride_floats, size_t count, bool xcd,
-                                hipStream_t stream);
+                                hipStream_t stream, int body = 1);
 
 // ---- fftcc3d.hip -----------------------------------------------------------
 struct Fftcc3dParams {
