@@ -27,7 +27,10 @@ AB_ONLY_SOURCES = ["icgn3d_rows.hip", "icgn2d_band.hip", "fftcc3d_fused_r5.hip"]
 AB_DEPENDENT = ["capi.hip", "icgn2d.hip", "icgn3d.hip"]
 AB_LIBDIR = os.path.join(LIBDIR, "ab")
 AB_LIB = os.path.join(AB_LIBDIR, "libopencorr_hip_ab.so")
-HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "dic2d_device.h", "fft_device.h", "fftcc2d_fusedn_impl.h", "fftcc3d_planes_impl.h", "icgn3d_device.h", os.path.join("..", "..", "include", "opencorr_hip.h")]
+HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "dic2d_device.h", "fft_device.h", "fftcc2d_fusedn_impl.h", "fftcc3d_planes_impl.h", "icgn3d_device.h", os.path.join("..", "..", "include", "opencorr_hip.h"),
+           # host logic without HIP calls; in a subfolder, so that kernel_fingerprint()'s listing of csrc/ (no PMC record goes stale
+           # from a host-only change) does not see them
+           os.path.join("host", "single_combiner.h"), os.path.join("host", "chunk_pipeline.h")]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP vectoriser pairs independent scalar fp32 operations into v_pk_mul_f32 / v_pk_add_f32.  On gfx950 a
 # packed op occupies a SIMD for 4.3 cycles against 2.4 for the plain one (profiles/r02b_valu_ubench.json) -- a 10 % gain that the

@@ -1359,10 +1359,10 @@ static void hint_single_poi_loop(oc_hip_engine* e) {
 // One batch of combined single-POI requests through the engine's host-queue path: records gathered into one buffer, ONE
 // compute call, records scattered back.  Requests with and without a centre offset cannot share a launch (the engine takes
 // an offset queue or none): the leader serves them as two sub-batches.
-static void serve_single_batch(oc_hip_engine* e, std::vector<oc_hip_engine::SingleRequest*>& batch) {
+static void serve_single_batch(oc_hip_engine* e, std::vector<oc_hip_engine::SingleCombiner::Request*>& batch) {
     const size_t rec = e->poi_bytes();
     for (int with_off = 0; with_off < 2; with_off++) {
-        std::vector<oc_hip_engine::SingleRequest*> part;
+        std::vector<oc_hip_engine::SingleCombiner::Request*> part;
         for (auto* r : batch)
             if ((r->offset != nullptr) == (with_off != 0)) part.push_back(r);
         if (part.empty()) continue;
@@ -1402,77 +1402,14 @@ static void serve_single_batch(oc_hip_engine* e, std::vector<oc_hip_engine::Sing
     }
 }
 
-// compute(POI*) / compute(POI*, center_offset): queue the request.  Whoever finds no leader becomes one: it takes everything
-// that is queued as ONE batch, serves it, wakes the owners of the served requests (each on its own condition variable) and
-// goes on with what has arrived meanwhile -- back to back, so the GPU never waits for a thread to wake up.  Its own request
-// sits in its first batch; after kSingleExtraBatches further batches it promotes the owner of a queued request to leader and
-// returns (no caller serves the others for ever).  A POI's result does not depend on the batch it travels in (the per-POI
-// solves are independent: tests/test_gpu_parity_2d.py::test_host_pipeline_chunks_change_no_bits).
-constexpr int kSingleExtraBatches = 32;
-
+// compute(POI*) / compute(POI*, center_offset): the request joins whatever batch the engine's combiner forms next
+// (host/single_combiner.h: the protocol and its invariants).  A POI's result does not depend on the batch it travels in (the
+// per-POI solves are independent: tests/test_gpu_parity_2d.py::test_host_pipeline_chunks_change_no_bits).
 static int compute_single(oc_hip_engine* e, void* poi, const float* offset) {
     if (!poi) return fail(OC_HIP_ERR_INVALID, "null POI");
     if (!e->single_combine) return compute_impl(e, poi, offset, 1, e->poi_bytes(), OC_HIP_HOST);
-    oc_hip_engine::SingleRequest req(poi, offset);
-    bool lead;
-    {
-        std::lock_guard<std::mutex> lk(e->single_mu);
-        e->single_pending.push_back(&req);
-        lead = !e->single_leader;
-        if (lead) e->single_leader = true;
-    }
-    // Publishing a request's new state is the leader's LAST access to it (the owner may return at once).  Owners whose spin
-    // budget ran out sleep on the engine's condition variable: they register under its mutex and re-check their state there, the
-    // leader takes the same mutex after its stores -- no wake-up is lost, and nobody pays a futex call while everyone spins.
-    auto wake_sleepers = [&]() {
-        if (e->single_sleepers.load(std::memory_order_acquire) > 0) {
-            std::lock_guard<std::mutex> ls(e->single_sleep_mu);
-            e->single_sleep_cv.notify_all();
-        }
-    };
-    if (!lead) {
-        // a short busy wait (the batch in flight is usually ~50 us from done), then polite polling -- yielding the core between
-        // looks, so that 60 waiting threads do not crowd out the leader and the HIP runtime's own threads --, then sleep
-        for (int spin = 0; spin < 1500 && req.state.load(std::memory_order_acquire) == 0; spin++) __builtin_ia32_pause();
-        if (req.state.load(std::memory_order_acquire) == 0) {
-            const auto t0 = std::chrono::steady_clock::now();
-            while (req.state.load(std::memory_order_acquire) == 0 && std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(400))
-                std::this_thread::yield();
-        }
-        if (req.state.load(std::memory_order_acquire) == 0) {
-            std::unique_lock<std::mutex> ls(e->single_sleep_mu);
-            e->single_sleepers.fetch_add(1, std::memory_order_acq_rel);
-            e->single_sleep_cv.wait(ls, [&] { return req.state.load(std::memory_order_acquire) != 0; });
-            e->single_sleepers.fetch_sub(1, std::memory_order_acq_rel);
-        }
-        lead = req.state.load(std::memory_order_acquire) == 2;   // promoted while still queued: this thread leads now
-    }
-    if (lead) {
-        std::vector<oc_hip_engine::SingleRequest*> batch;
-        bool own_done = false;
-        for (int served = 0;; served++) {
-            {
-                std::lock_guard<std::mutex> lk(e->single_mu);
-                if (e->single_pending.empty()) {
-                    e->single_leader = false;   // (its own request was queued before this thread became leader: it is done)
-                    break;
-                }
-                if (own_done && served > kSingleExtraBatches) {
-                    e->single_pending.front()->state.store(2, std::memory_order_release);   // its owner takes over; the request stays queued
-                    wake_sleepers();
-                    break;
-                }
-                batch.clear();
-                batch.swap(e->single_pending);
-            }
-            serve_single_batch(e, batch);
-            for (auto* r : batch) {
-                if (r == &req) own_done = true;
-                else r->state.store(1, std::memory_order_release);
-            }
-            wake_sleepers();
-        }
-    }
+    oc_hip_engine::SingleCombiner::Request req(poi, offset);
+    e->single_combiner.submit(req, [e](std::vector<oc_hip_engine::SingleCombiner::Request*>& batch) { serve_single_batch(e, batch); });
     if (req.rc != OC_HIP_OK) return fail(req.rc, "%s", req.error.c_str());
     return OC_HIP_OK;
 }

@@ -27,44 +27,9 @@ int compute_host(oc_hip_engine* e, char* pois, const float* offsets, size_t coun
     const size_t bytes = count * stride_bytes;
     OC_TRY(e->poi_stage.reserve(bytes));
     if (offsets) OC_TRY(e->off_stage.reserve(count * 2 * sizeof(float)));
-    // Chunk schedule.  What a pipeline cannot hide is the copy-in of its FIRST chunk and the copy-out of its LAST one, and
-    // every extra chunk costs a launch tail (the ICGN kernels' last workgroups run on a half-empty chip) plus an
-    // inter-stream hand-over.  So: small chunks at both ends (half of "host_chunk"), few large ones (three times
-    // "host_chunk") in between, whose copies hide behind the neighbours' kernels.  Measured on config B (250 000 POIs,
-    // chain of FFTCC2D + ICGN2D1): uniform chunks of 65 536: 4.76 ms, one piece: 5.36 ms, this schedule: see DESIGN 4.4.
-    std::vector<std::pair<size_t, size_t>> sched;  // (first POI, POIs)
-    {
-        const size_t unit = e->host_chunk > 0 ? (size_t)e->host_chunk : count;
-        // A lone FFTCC engine (the first call of the reference's unmodified `fftcc->compute(q); icgn->compute(q);`) is
-        // TRANSFER bound: 0.44 ms of kernel between 0.5 ms in and 0.5 ms out on config B.  There the copies of the two
-        // directions should overlap each other (PCIe is full duplex): uniform chunks of half a unit -- with the edge / middle
-        // schedule below the big middle chunk's copy-in, kernel and copy-out run one after the other (round 6: two-call
-        // sequence 5.0 -> see DESIGN 4.6).
-        const bool transfer_bound = n_chain == 0 && (e->kind == OC_HIP_FFTCC2D || e->kind == OC_HIP_FFTCC3D);
-        if (transfer_bound && e->host_chunk > 0 && count >= unit) {
-            const size_t piece = std::max<size_t>(unit / 2, 1), np = (count + piece - 1) / piece;
-            size_t at = 0;
-            for (size_t i = 0; i < np; i++) {
-                const size_t n = count / np + (i < count % np ? 1 : 0);
-                sched.emplace_back(at, n);
-                at += n;
-            }
-        } else if (count < 2 * unit) {
-            sched.emplace_back(0, count);  // not worth a pipeline
-        } else {
-            const size_t edge = std::max<size_t>(unit / 2, 1), mid_max = 3 * unit;
-            sched.emplace_back(0, edge);
-            size_t at = edge;
-            const size_t mid_total = count - 2 * edge;
-            const size_t nmid = (mid_total + mid_max - 1) / mid_max;
-            for (size_t i = 0; i < nmid; i++) {
-                const size_t n = mid_total / nmid + (i < mid_total % nmid ? 1 : 0);
-                sched.emplace_back(at, n);
-                at += n;
-            }
-            sched.emplace_back(at, count - at);
-        }
-    }
+    // (a lone FFTCC engine is transfer bound: host/chunk_pipeline.h)
+    const bool transfer_bound = n_chain == 0 && (e->kind == OC_HIP_FFTCC2D || e->kind == OC_HIP_FFTCC3D);
+    const std::vector<std::pair<size_t, size_t>> sched = ochip_host::chunk_schedule(count, e->host_chunk, transfer_bound);  // (first POI, POIs)
     const size_t nchunk = sched.size();
     if (nchunk > 1) {
         if (!e->copy_stream) OC_HIP_TRY(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
@@ -99,17 +64,7 @@ int compute_host(oc_hip_engine* e, char* pois, const float* offsets, size_t coun
     // chunk's event and copies its records back.
     const int device = e->device;
     hipError_t out_err = hipSuccess;
-    {
-        std::lock_guard<std::mutex> hand(e->feed_mu);
-        e->chunks_fed = 0;
-    }
-    auto hand_over = [&](size_t fed) {
-        {
-            std::lock_guard<std::mutex> hand(e->feed_mu);
-            e->chunks_fed = fed;
-        }
-        e->feed_cv.notify_one();
-    };
+    e->chunk_handoff.reset();
     auto copy_out = [&] {
         if (hipSetDevice(device) != hipSuccess) {
             out_err = hipErrorInvalidDevice;
@@ -119,11 +74,7 @@ int compute_host(oc_hip_engine* e, char* pois, const float* offsets, size_t coun
             const size_t first = sched[c].first, n = sched[c].second;
             // the event is recorded by the feeding thread after chunk c's kernels were enqueued; until then
             // hipStreamWaitEvent would see the event of an earlier call, so sleep until the hand-off
-            {
-                std::unique_lock<std::mutex> hand(e->feed_mu);
-                e->feed_cv.wait(hand, [&] { return e->chunks_fed > c; });
-                if (e->chunks_fed == (size_t)-1) break;  // the feeder failed: drain what was issued and stop
-            }
+            if (!e->chunk_handoff.wait_for(c)) break;  // the feeder failed: stop
             out_err = hipStreamWaitEvent(e->copy_stream, e->chunk_done[c], 0);
             if (out_err == hipSuccess)
                 out_err = hipMemcpyAsync(pois + first * stride_bytes, stage + first * stride_bytes, n * stride_bytes, hipMemcpyDeviceToHost,
@@ -161,13 +112,13 @@ int compute_host(oc_hip_engine* e, char* pois, const float* offsets, size_t coun
             OC_HIP_TRY(hipStreamWaitEvent(e->stream, e->chunk_in[c], 0));
             OC_TRY(run_all(reinterpret_cast<float*>(stage + first * stride_bytes), n, d_off));
             OC_HIP_TRY(hipEventRecord(e->chunk_done[c], e->stream));
-            hand_over(c + 1);
+            e->chunk_handoff.hand_over(c + 1);
         }
         return OC_HIP_OK;
     };
     rc = feed();
     const std::string feed_error = g_last_error;
-    if (rc != OC_HIP_OK) hand_over((size_t)-1);
+    if (rc != OC_HIP_OK) e->chunk_handoff.fail();
     if (helper) out_thread.join();
     else copy_out();
     OC_HIP_TRY(hipStreamSynchronize(e->stream));

@@ -1,6 +1,7 @@
 // capi_internal.h -- what the translation units of the C-ABI (capi.hip: engines and entry points; capi_host.hip: the chunked
 // host-queue pipeline; capi_group.hip: device groups + the RCCL binding; capi_strain.hip: Strain / RegionFit and the reliable /
 // unreliable selection) share: the engine object, device buffers, error reporting, the stream / tail-event helpers.
+// host/*.h: host logic without HIP calls (the single-POI combiner, the chunk schedule and hand-off), standard headers only.
 #pragma once
 #include "../../include/opencorr_hip.h"
 
@@ -49,6 +50,8 @@ ncclResult_t ncclGetVersion(int* version);
 #endif
 
 #include "oc_kernels.h"
+#include "host/chunk_pipeline.h"
+#include "host/single_combiner.h"
 
 namespace ochip_capi {
 
@@ -260,32 +263,20 @@ struct oc_hip_engine {
     std::vector<hipEvent_t> split_ev;
     int icgn2d_split_chunks = 0;
     std::vector<hipEvent_t> chunk_done, chunk_in;
-    size_t chunks_fed = 0;  // chunks whose kernels (and event) are enqueued; (size_t)-1: the feeder failed.  Guarded by feed_mu
-    std::mutex feed_mu;
-    std::condition_variable feed_cv;  // the copy-out thread sleeps here until the next chunk has been handed over
+    ochip_host::ChunkHandoff chunk_handoff;  // the copy-out thread sleeps here until the next chunk has been handed over
     int host_chunk = 65536;  // POIs per chunk ("host_chunk" tuning key; 0 = the whole queue at once)
     std::atomic<unsigned> single_calls{0};  // compute(POI*) calls on this engine (one hint on stderr when a caller loops over them)
-    // Combining front end of compute(POI*) (round 6): the reference's single-POI form is called from the CALLER's own OpenMP
-    // loops (src/oc_epipolar_search.cpp:184-188, relying on one scratch instance per thread, src/oc_icgn.cpp:61-69,147).
-    // Callers that arrive while a launch is in flight are queued; one of them (the leader) hands the whole batch to the
-    // engine as ONE queue -- T threads cost one launch per ~T POIs instead of T serialised launches.
-    struct SingleRequest {
+    // Combining front end of compute(POI*) (host/single_combiner.h): callers that arrive while a launch is in flight are queued;
+    // one of them (the leader) hands the whole batch to the engine as ONE queue (serve_single_batch, capi.hip).
+    struct SinglePoi {
         void* poi;
         const float* offset;
         int rc = OC_HIP_OK;
         std::string error;
-        // The owner spins on `state` (a batch takes ~50 us: cheaper than a futex round trip per served thread), then sleeps on the
-        // ENGINE's condition variable.  The leader's last access to a request is the store to `state`: once it is non-zero the
-        // owner may return and the request is gone.
-        std::atomic<int> state{0};   // 0 = queued, 1 = served, 2 = promoted to leader while still queued
-        SingleRequest(void* p, const float* o) : poi(p), offset(o) {}
+        SinglePoi(void* p, const float* o) : poi(p), offset(o) {}
     };
-    std::mutex single_mu;
-    std::mutex single_sleep_mu;                  // sleepers of the front end (owners whose spin budget ran out)
-    std::condition_variable single_sleep_cv;
-    std::atomic<int> single_sleepers{0};
-    std::vector<SingleRequest*> single_pending;
-    bool single_leader = false;
+    using SingleCombiner = ochip_host::SingleCombiner<SinglePoi>;
+    SingleCombiner single_combiner;
     int single_combine = 1;                      // "single_combine" tuning key: 0 = every call a launch of its own (the round-5 behaviour)
     std::atomic<unsigned long long> single_batches{0}, single_batched_pois{0}, single_engine_ns{0};   // (engine_ns: time inside the engine calls)
     PinnedBuf single_buf, single_off;            // the leader's contiguous, page-locked copy of a batch's records (and offsets)
