@@ -363,13 +363,18 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     workgroup); -1 (default) lets the engine choose: 5 / 4 (6 / 12 DoF: coordinate table, lockstep sweeps,
  *                     8-wave workgroups) for queues >= 32768 POIs of subsets up to 35 x 34 / 41 x 41, 2 / 3 (no table) below,
  *                     7 (target array only) for self-adaptive subsets from 27 passes up (2 / 3 below), 1 (single-wave
- *                     workgroups) for what fits nothing else.  0, 6, 8 (the split launch shape) and 9 (the workgroup's
+ *                     workgroups) for what fits nothing else.  10 / 11 (6 / 12 DoF): the lockstep sweeps in 4-WAVE workgroups, six /
+ *                     four per CU, on a coordinate table of 6 instead of 12 bytes per sample (byte offset, 8-bit column and
+ *                     row); both use the set-up cache.  They apply to launches with one radius pair (no self-adaptive radii, no
+ *                     IC-LM), subsets of at most 256 x 256 whose six / four workgroups fit a CU's LDS (19 / 28 passes of 64
+ *                     samples: 35 x 34 / 41 x 41); any other launch takes the automatic choice instead, with the same bits.
+ *                     For queues >= 32768 POIs the automatic choice takes them in place of 5 / 4 wherever they apply.  0, 6, 8 (the split launch shape) and 9 (the workgroup's
  *                     coefficient band staged in LDS, icgn2d_band.hip) are measured losers that only the A/B build of the
  *                     library contains
  *   "icgn2d_xcd"      1 (default): workgroups of one XCD serve a contiguous range of the POI queue
  *   "icgn2d_tile_px"  side of the square image tiles the ICGN2D / NR2D1 queue is visited by (L1 / L2 locality; default 128;
  *                     0 = queue order; applied to queues >= 16384 POIs)
- *   "icgn2d_setup_cache"  1 (default): ICGN2D1 / ICGN2D2 keep the per-POI set-up of their big-queue launches (variants 5 / 4) --
+ *   "icgn2d_setup_cache"  1 (default): ICGN2D1 / ICGN2D2 keep the per-POI set-up of their big-queue launches (variants 10 / 11, 5 / 4) --
  *                     reference mean, norm and inverse Hessian: 152 + 8 B per POI at 6 DoF, 584 + 8 B at 12 -- from one compute()
  *                     to the next and start from it while reference, gradients, radii, arithmetic, count, stride and the
  *                     queue's (x, y) stay what they were: the sequence "overwrite the target in place, prepare_tar(), compute()"
@@ -495,6 +500,11 @@ int oc_hip_profile_reset(oc_hip_engine* engine);
 #define OC_HIP_SETUP_CACHE_FILL 1
 #define OC_HIP_SETUP_CACHE_USE 2
 int oc_hip_icgn2d_setup_cache_last(oc_hip_engine* engine, int* state);
+/* The on-chip limits of an "icgn2d_variant" id (no engine, no device needed): *max_samples = the largest (2 rx + 1) (2 ry + 1)
+ * its LDS layout holds (0 for variant 9, which has its own rule); *compact_admissible = 0 when the id is not 10 or 11 or the
+ * radii do not fit it (see the key), 1 when they fit but `count` is below what the automatic choice asks for (the id still
+ * runs when it is named), 2 when the automatic choice may take it. */
+int oc_hip_icgn2d_variant_limits(int variant, int radius_x, int radius_y, size_t count, int* max_samples, int* compact_admissible);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@ SYMBOLS = [
     "oc_hip_set_self_adaptive", "oc_hip_synchronize", "oc_hip_select_best", "oc_hip_split_reliable", "oc_hip_merge_recovered",
     "oc_hip_get_kind", "oc_hip_get_field", "oc_hip_read_field",
     "oc_hip_profile_enable", "oc_hip_profile_read", "oc_hip_profile_reset", "oc_hip_icgn2d_setup_cache_last",
+    "oc_hip_icgn2d_variant_limits",
     "oc_hip_set_devices", "oc_hip_get_devices", "oc_hip_group_queue",
     "oc_hip_calibration_create", "oc_hip_calibration_set_undistortion", "oc_hip_calibration_prepare", "oc_hip_calibration_get",
     "oc_hip_calibration_maps", "oc_hip_calibration_undistort",
@@ -171,6 +172,7 @@ def lib():
     L.oc_hip_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.oc_hip_profile_reset.argtypes = [vp]
     L.oc_hip_icgn2d_setup_cache_last.argtypes = [vp, ctypes.POINTER(i)]
+    L.oc_hip_icgn2d_variant_limits.argtypes = [i, i, i, sz, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.oc_hip_set_devices.argtypes = [vp, ctypes.POINTER(i), i]
     L.oc_hip_get_devices.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(i)]
     L.oc_hip_group_queue.argtypes = [vp, i, pp, ctypes.POINTER(sz)]

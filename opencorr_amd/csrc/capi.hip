@@ -245,6 +245,12 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     const long long N = (2LL * rx + 1) * (2LL * ry + 1);
     // fall back to the LDS-light single-wave variant when the tuned one cannot hold the subset
     int variant = e->icgn2d_variant;
+    // Variants 10 / 11 (4-wave lockstep workgroups on the compact coordinate table, six / four per CU): one radius per launch, 8-bit
+    // column and row indices, every one of those workgroups inside a CU's LDS -- a launch that is not all of that takes the
+    // automatic choice below instead, silently and with the same bits (which takes them for queues >= 32768 POIs only)
+    const bool compact_ok = !lm && !e->self_adaptive;
+    if ((variant == 10 || variant == 11) && !(compact_ok && ochip::icgn2d_compact_fits(variant, rx, ry))) variant = -1;
+    const bool chosen = variant < 0;
     if (variant < 0) {
         // ICGN2D1: the coordinate-table variant at 6 waves per SIMD while three of its workgroups fit a CU's LDS (subsets up
         // to 19 passes of 64 samples, i.e. 35 x 34), the LDS-light 4-wave workgroups beyond; ICGN2D2: see below
@@ -254,13 +260,21 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
         // ICGN2D2: the table variant in 8-wave workgroups while two of them fit a CU (up to 28 passes: 41 x 41), measured
         // 3.65 against 3.81 ms on config C (profiles/r03q_icgn2d2_variant_ab_configC.json)
         variant = dof == 12 ? (passes <= 28 && count >= 32768 ? 4 : 3) : (passes <= 19 && count >= 32768 ? 5 : 2);
+        // ... and in their place, where they are admissible, the same sweeps in 4-wave workgroups on the compact table, six /
+        // four per CU: interleaved on MI355X (profiles/r11a_icgn2d_4wave_compact_table_ab.json) config B 2.49 against 2.59 ms
+        // and config C 2.30 against 2.42 ms per launch served by the set-up cache, 2.86 / 2.91 and 3.25 / 3.41 without it
+        constexpr bool kCompactDefault[2] = {true, true};   // [0] ICGN2D1: 10 for 5, [1] ICGN2D2: 11 for 4
+        const int compact = dof == 12 ? 11 : 10;
+        if ((variant == 4 || variant == 5) && kCompactDefault[dof == 12] && compact_ok &&
+            ochip::icgn2d_compact_admissible(compact, rx, ry, count))
+            variant = compact;
     }
     // per-POI radii: no shared coordinate table, and the per-wave arrays are sized for the LARGEST subset of the batch -- the
     // target-array-only shape (variant 7) keeps four workgroups on a CU where variant 2 holds two (bench.py paths_8f_row1)
     // -- when variant 2's two arrays per wave would leave a CU at most two workgroups (subsets from 26 passes = 41 x 40 up: the
     // measured case, radii 12 ... 20: 4.91 -> 3.98 ms); smaller batches keep variant 2, which is 4 % ahead at equal occupancy
     // (3.49 vs 3.61 ms on a uniform r = 16: one image read per sample fewer).  ADVICE r5.
-    if (e->self_adaptive && (e->icgn2d_variant < 0 || ochip::icgn2d_variant_uses_table(variant))) {
+    if (e->self_adaptive && (chosen || ochip::icgn2d_variant_uses_table(variant))) {
         const long long passes_sa = (N + 63) / 64;
         const bool crowded = 3 * (2 * 4 * passes_sa * 256) > (160 * 1024 - 2048);   // three workgroups of variant 2 no longer fit
         variant = crowded ? 7 : (dof == 12 ? 3 : 2);
@@ -294,7 +308,8 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     // coordinates the records were built for is decided on the device by the check in front of the launch.  Centre offsets,
     // self-adaptive radii, IC-LM and the small-queue variants go around it.
     e->setup_cache_last = 0;
-    const bool cached = e->icgn2d_setup_cache && !onepass && !lm && !band && !d_offsets && !e->self_adaptive && (variant == 4 || variant == 5) &&
+    const bool cached = e->icgn2d_setup_cache && !onepass && !lm && !band && !d_offsets && !e->self_adaptive &&
+                        (variant == 4 || variant == 5 || variant == 10 || variant == 11) &&
                         count <= kMaxGrid;
     oc_hip_engine::SetupCacheKey cache_key;
     bool cache_hit = false;
@@ -1561,6 +1576,15 @@ int oc_hip_icgn2d_setup_cache_last(oc_hip_engine* e, int* state) {
         OC_HIP_TRY(hipMemcpy(&word, e->setup_cache_word.p, sizeof(word), hipMemcpyDeviceToHost));
         *state = word == e->setup_cache_epoch ? OC_HIP_SETUP_CACHE_FILL : OC_HIP_SETUP_CACHE_USE;
     }
+    return OC_HIP_OK;
+}
+
+int oc_hip_icgn2d_variant_limits(int variant, int radius_x, int radius_y, size_t count, int* max_samples, int* compact_admissible) {
+    if (!max_samples || !compact_admissible) return fail(OC_HIP_ERR_INVALID, "null argument");
+    if (variant < 0 || variant >= ochip::icgn2d_variant_count())
+        return fail(OC_HIP_ERR_INVALID, "icgn2d_variant %d out of range [0, %d)", variant, ochip::icgn2d_variant_count());
+    *max_samples = ochip::icgn2d_max_samples(variant);
+    *compact_admissible = ochip::icgn2d_compact_admissible(variant, radius_x, radius_y, count) ? 2 : ochip::icgn2d_compact_fits(variant, radius_x, radius_y) ? 1 : 0;
     return OC_HIP_OK;
 }
 

@@ -19,6 +19,10 @@
 //     bicubic table (four buffer_load_b128, one per plane) -- the "interpolation sweep" -- except while the warp is an integer
 //     translation (the first iteration of every FFTCC guess): such a sweep reads 4 B / sample from the table's value plane
 //     and evaluates nothing (`kIntSweep`, tuning key "icgn2d_int_first").
+// Since the compact table (MODE 6, variants 10 / 11) large queues run the SAME kernel body in FOUR-wave workgroups, six per CU
+// (still 6 waves per SIMD): the table holds a byte offset and an 8-bit column and row per sample slot, every wave inverts its
+// own Hessian (no cooperative inverse), everything else -- lockstep barrier, set-up cache, integer-translation sweep -- as above;
+// variant 5 remains for subsets of more than 256 rows or columns.
 // Other variants (oc_hip_set_tuning("icgn2d_variant")): 4-wave workgroups without table or barriers for small queues and
 // large subsets (variant 2), one-wave workgroups with everything parked in LDS (variants 0, 1, 3, and the IC-LM engines).
 // Reductions (mean, norms, Hessian, numerator, ZNSSD) are per-lane partial sums in increasing s followed by the xor
@@ -114,6 +118,8 @@ namespace ochip {
 //   MODE 2 (round 5):         ts[NT*64] only, NO table -- MODE 4's footprint for queues that cannot share a table, i.e.
 //                             self-adaptive subsets: the arrays are sized for the LARGEST subset of the batch, so halving
 //                             them is what keeps four workgroups on a CU when radii reach 20 (27 passes).
+//   MODE 6:                   MODE 4 on the compact table (byte offset + 8-bit column and row per slot: 1.5 floats instead
+//                             of 3) -- the 4-wave lockstep workgroups of variants 10 and 11.  (5 names the band kernel.)
 //   TAB: one table per WORKGROUP of what depends on (lane, pass) only -- the sample's local coordinates as a float
 //        pair and its byte offset from the subset origin -- filled once by the workgroup's waves: the per-sample
 //        walk (wrap test, selects) and the int -> float conversions of every pass become one or two LDS reads.
@@ -173,8 +179,11 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NH = DOF * (DOF + 1) / 2;
     constexpr bool TAB = MODE >= 3;
-    constexpr bool KEEP_RS = MODE != 4 && MODE != 2;  // the zero-mean reference subset is parked in LDS
-    constexpr int ARRAYS = MODE == 0 ? 4 : ((MODE == 4 || MODE == 2) ? 1 : 2);
+    // MODE 6 = MODE 4 with the COMPACT coordinate table (6 instead of 12 bytes per sample slot, see the table fill below)
+    constexpr bool kTabTarget = MODE == 4 || MODE == 6;  // per-workgroup table + the target array only
+    constexpr bool kCompactTab = MODE == 6;
+    constexpr bool KEEP_RS = !kTabTarget && MODE != 2;  // the zero-mean reference subset is parked in LDS
+    constexpr int ARRAYS = MODE == 0 ? 4 : ((kTabTarget || MODE == 2) ? 1 : 2);
     // ICGN2D1 in 8-wave workgroups: the eight 6 x 6 Hessians are inverted by ONE wave (coop_inverse6_x8); two more
     // barriers, which every wave passes exactly once -- also the ones that abandon their POI early (leave())
     constexpr bool COOP = MODE == 4 && DOF == 6 && LM == 0 && WPB == 8 && PHASE != 2;
@@ -190,12 +199,14 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     // FILL launch a wave that fails only the data part of the guard (u, v, zncc) still runs the set-up and files its record
     // -- it passes COOP's barriers on the ordinary path, before any sweep barrier -- so that invariant (b) below holds in
     // both kinds of launch and a POI rejected now finds its record when a later call accepts it.
-    constexpr bool CACHE = MODE == 4 && LM == 0 && PHASE == 0 && WPB == 8 && OFFS == 0;
+    // (the 4-wave workgroups of the compact-table variants 10 and 11 take part as well: their waves invert on their own, so a
+    // USE launch simply has nothing to skip but the set-up itself)
+    constexpr bool CACHE = ((MODE == 4 && WPB == 8) || (MODE == 6 && WPB == 4)) && LM == 0 && PHASE == 0 && OFFS == 0;
     constexpr int kSetupFloats = icgn2d_setup_floats(DOF);
     // lockstep sweeps (see OC_SWEEP_BARRIER above): the 8-wave table variants -- one subset size per launch, so every live
     // wave of a workgroup runs the same number of pass groups
     // (the 6-DoF kernel with only two workgroups per CU, variant 4, loses 6 % with them: it keeps them off by default)
-    constexpr int SWEEP_SYNC = (MODE == 4 && LM == 0 && PHASE != 1 && (WPB == 8 || WPB == 4))
+    constexpr int SWEEP_SYNC = (kTabTarget && LM == 0 && PHASE != 1 && (WPB == 8 || WPB == 4))
                                    ? (OC_SWEEP_BARRIER < 0 ? (DOF == 6 ? ((OCC >= 6 || WPB == 4) ? 2 : 0) : 3) : OC_SWEEP_BARRIER)
                                    : 0;
     // What keeps the sweep barriers deadlock-free although the waves of a workgroup run different iteration counts and may
@@ -259,16 +270,22 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
             __syncthreads();
         }
     };
-    // TAB: [NTA*64] float pairs (x_local, y_local), then [NTA*64] byte offsets; the waves' own arrays follow
+    // TAB: [NTA*64] float pairs (x_local, y_local), then [NTA*64] byte offsets; the waves' own arrays follow.
+    // The compact table (MODE 6): [NTA*64] byte offsets, then [NTA*64] 16-bit (column | row << 8) -- 6 bytes per slot instead of
+    // 12, which is what lets six 4-wave workgroups share a CU's LDS at r = 16; the host admits it for subsets of at most 256
+    // columns and 256 rows.  The waves' arrays start NTA * 384 bytes in: still 16-byte aligned.
     f2* __restrict__ tab_xy = reinterpret_cast<f2*>(lds);
-    unsigned* __restrict__ tab_off = reinterpret_cast<unsigned*>(lds + 2 * NTA * kWave);
-    float* const wave_lds = lds + (TAB ? 3 * NTA * kWave : 0);
+    unsigned* __restrict__ tab_off = reinterpret_cast<unsigned*>(lds + (kCompactTab ? 0 : 2 * NTA * kWave));
+    unsigned short* __restrict__ tab_rc = reinterpret_cast<unsigned short*>(lds + NTA * kWave);
+    float* const wave_lds = lds + (kCompactTab ? 3 * NTA * (kWave / 2) : TAB ? 3 * NTA * kWave : 0);
     if constexpr (TAB) {
         const int Wt = 2 * P.rx + 1;
         const unsigned w4t = (unsigned)P.width * 4u;
         for (int s = threadIdx.x; s < NTA * kWave; s += kWave * WPB) {
             const int r = s / Wt, c = s - r * Wt;
-            tab_xy[s] = mk2((float)(c - P.rx), (float)(r - P.ry));
+            // (slots past the subset's last sample may hold a row above 255, cut to 16 bits here: no pass uses their value)
+            if constexpr (kCompactTab) tab_rc[s] = (unsigned short)((unsigned)c | ((unsigned)r << 8));
+            else tab_xy[s] = mk2((float)(c - P.rx), (float)(r - P.ry));
             tab_off[s] = (unsigned)r * w4t + ((unsigned)c << 2);
         }
         __syncthreads();  // waves that leave early below are past this barrier (and pass COOP's two in leave())
@@ -347,7 +364,17 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
     auto soff = [&](const SampleWalk& w) { return __umul24((unsigned)w.r, w4) + ((unsigned)w.c << 2); };
 
     // per-pass sample coordinates: from the workgroup's table, or walked
-    auto tab_at = [&](int t) { return tab_xy[t * kWave + lane]; };
+    // Compact table: (float)c - (float)rx has the bits of (float)(c - rx).  c, rx and c - rx are integers below 2^24 in
+    // magnitude, so both conversions and the subtraction are exact, and a zero difference of two equal positive floats is +0
+    // under round-to-nearest, which is what (float)0 gives.  Likewise for the row.
+    auto tab_at = [&](int t) {
+        if constexpr (kCompactTab) {
+            const unsigned rc = tab_rc[t * kWave + lane];
+            return mk2((float)(rc & 255u) - (float)rx, (float)(rc >> 8) - (float)ry);
+        } else {
+            return f2(tab_xy[t * kWave + lane]);
+        }
+    };
     auto off_at = [&](int t) { return tab_off[t * kWave + lane]; };
 
     // ---- reference subset, zero-mean + norm (src/oc_icgn.cpp:174-176, src/oc_subset.cpp:39-53)
@@ -1169,8 +1196,9 @@ struct VariantInfo {
 template <int DOF, int G, int MODE, int PIPE, int WPB, int OCC, int OFFS, int LM = 0, int PHASE = 0>
 static hipError_t launch_t(const Icgn2dParams& p, float* pois, int stride_f, size_t count, int nt, bool xcd,
                            hipStream_t stream) {
-    constexpr int arrays = PHASE == 1 ? 0 : (MODE == 0 ? 4 : ((MODE == 4 || MODE == 2) ? 1 : 2));  // (the set-up kernel: table only)
-    size_t lds = ((size_t)arrays * WPB + (MODE >= 3 ? 3 : 0)) * nt * kWave * sizeof(float);
+    constexpr int arrays = PHASE == 1 ? 0 : (MODE == 0 ? 4 : ((MODE == 4 || MODE == 6 || MODE == 2) ? 1 : 2));  // (the set-up kernel: table only)
+    // (in half floats per sample slot: the table takes 3 floats, the compact one of MODE 6 a float and a half)
+    size_t lds = ((size_t)2 * arrays * WPB + (MODE == 6 ? 3 : MODE >= 3 ? 6 : 0)) * nt * kWave * (sizeof(float) / 2);
     if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
 #if OC_BUILD_AB
     // experiments only, A/B build only (tools/icgn2d_occupancy_probe.py): OC_ICGN2D_LDS_PAD=<bytes> raises the workgroup's LDS
@@ -1216,6 +1244,9 @@ static hipError_t launch_t(const Icgn2dParams& p, float* pois, int stride_f, siz
 //    fewer waves per SIMD): 3.47 against 3.30 ms (profiles/r4i_icgn2d1_variant_ab_4wave_lockstep.json) -- not selected automatically.
 //    7 (round 5): variant 2 with the target array only (MODE 2) -- the self-adaptive default: half the LDS, so that a batch
 //    whose largest subset is 41 x 41 still runs four 4-wave workgroups per CU instead of two.
+//    10, 11: variant 6's 4-wave lockstep workgroups on the compact table (MODE 6): six per CU at 80 VGPRs for ICGN2D1 (the
+//    24 waves of variant 5 as six independent workgroups instead of three), four per CU at 128 VGPRs for ICGN2D2; both use the
+//    set-up cache.  capi.hip admits them for subsets of at most 256 x 256 whose workgroups all fit a CU.
 // Round 1's G = 2 and software-pipelined variants never won a sweep and are gone.
 // Variants 0, 6 and 8 are measured losers kept as A/B partners: they are compiled only into the A/B build of the library
 // (-DOC_BUILD_AB=1, opencorr_amd/build.py build_ab(); tests that compare them load that build).
@@ -1226,7 +1257,9 @@ static hipError_t launch_t(const Icgn2dParams& p, float* pois, int stride_f, siz
     X(3, 4, 1, 0, 1, 3)       \
     X(4, 3, 4, 0, 8, 4)       \
     X(5, OC_V5_G, 4, 0, 8, OC_V5_OCC) \
-    X(7, 3, 2, 0, 4, 4)
+    X(7, 3, 2, 0, 4, 4)       \
+    X(10, 2, 6, 0, 4, 6)      \
+    X(11, 3, 6, 0, 4, 4)
 #define OC_ICGN2D_VARIANTS_AB(X) \
     X(0, 3, 0, 0, 1, 1)       \
     X(6, 2, 4, 0, 4, 4)
@@ -1307,8 +1340,9 @@ hipError_t launch_iclm2d2(const Icgn2dParams& p, float* pois, int stride_f, size
 #if !OC_FMA
 // ---- the arithmetic-independent part and the dispatch between the two builds (this translation unit only) ----
 using OC_ARITH::kLdsBudget;
-constexpr int kIcgn2dVariants = 10;  // 0 ... 7: one kernel each; 8: the split launch shape (set-up kernel + iteration kernel);
-                                     // 9: the band kernel of icgn2d_band.hip (capi.hip launches it; listed here for the tuning key)
+constexpr int kIcgn2dVariants = 12;  // 0 ... 7: one kernel each; 8: the split launch shape (set-up kernel + iteration kernel);
+                                     // 9: the band kernel of icgn2d_band.hip (capi.hip launches it; listed here for the tuning key);
+                                     // 10, 11: 4-wave lockstep workgroups on the compact table (MODE 6), six / four per CU
 
 int icgn2d_variant_count() { return kIcgn2dVariants; }
 
@@ -1344,8 +1378,20 @@ int icgn2d_max_samples(int variant) {
     int g, mode, pipe, wpb, occ;
     if (icgn2d_variant_info(variant, &g, &mode, &pipe, &wpb, &occ)) return 0;
     if (variant == 9) return 0;  // (capi.hip asks icgn2d_band_supported instead)
-    const int arrays = mode == 0 ? 4 : ((mode == 4 || mode == 2) ? 1 : 2);
-    return kLdsBudget / ((arrays * wpb + (mode >= 3 ? 3 : 0)) * (int)sizeof(float) * kWave) * kWave;
+    const int arrays = mode == 0 ? 4 : ((mode == 4 || mode == 6 || mode == 2) ? 1 : 2);
+    // (half floats per sample slot, as in launch_t: the compact table of mode 6 takes 3 of them, the float table 6)
+    return kLdsBudget / ((2 * arrays * wpb + (mode == 6 ? 3 : mode >= 3 ? 6 : 0)) * ((int)sizeof(float) / 2) * kWave) * kWave;
+}
+
+bool icgn2d_compact_admissible(int variant, int rx, int ry, size_t count) { return count >= 32768 && icgn2d_compact_fits(variant, rx, ry); }
+
+bool icgn2d_compact_fits(int variant, int rx, int ry) {
+    if (variant != 10 && variant != 11) return false;
+    if (rx < 0 || ry < 0 || 2 * rx + 1 > 256 || 2 * ry + 1 > 256) return false;
+    const long long nt = ((2LL * rx + 1) * (2LL * ry + 1) + kWave - 1) / kWave;
+    // a workgroup: four target arrays of nt * 64 floats and the table's nt * 64 * 6 bytes (launch_t)
+    const long long lds = (4 * 4 + 6) * nt * kWave;
+    return (variant == 10 ? 6 : 4) * lds <= kLdsBudget;
 }
 
 int iclm2d_max_samples() { return kLdsBudget / (2 * (int)sizeof(float) * kWave) * kWave; }

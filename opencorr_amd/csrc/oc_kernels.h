@@ -38,7 +38,7 @@ struct Icgn2dParams {
     int arith_fma;  // 1: the build whose per-sample multiply-adds are fused (oc_device.h OC_FMA; oracle OC_ORDER_LANES_FMA)
     float* setup;   // variant 8 (split launch shape): icgn2d_setup_record_floats(dof) floats per POI -- mean, norm, H^-1 -- written by
                     // the set-up kernel and read by the iteration kernel; nullptr otherwise
-    // Set-up cache of the big-queue table variants (4, 5; icgn2d.hip): nullptr = off.  Otherwise icgn2d_setup_record_floats(dof)
+    // Set-up cache of the big-queue table variants (4, 5, 10, 11; icgn2d.hip): nullptr = off.  Otherwise icgn2d_setup_record_floats(dof)
     // floats per POI that outlive the call.  The launch FILLS them (and computes as ever) when cache_force_fill is set or
     // *cache_word == cache_epoch -- the stamp launch_poi2d_xy_check leaves when the queue's coordinates are not the ones the
     // records were built for -- and otherwise starts from them.
@@ -113,6 +113,12 @@ inline bool icgn2d_variant_uses_table(int variant) {
 }
 // largest (2rx+1)*(2ry+1) a variant accepts
 int icgn2d_max_samples(int variant);
+// Variants 10 / 11 (4-wave workgroups on the compact coordinate table): whether a launch with ONE radius pair can run them -- at
+// most 256 columns and 256 rows (the table keeps them as bytes) and all six (variant 10) / four (variant 11) workgroups of a CU
+// inside its LDS -- and whether the automatic choice may take them: that, and count >= 32768 (a queue named through the
+// tuning key runs them at any length, as it runs variants 4 and 5).  Self-adaptive radii and IC-LM are the caller's to exclude.
+bool icgn2d_compact_fits(int variant, int rx, int ry);
+bool icgn2d_compact_admissible(int variant, int rx, int ry, size_t count);
 
 // ---- poi_order.hip ---------------------------------------------------------
 // locality schedule: perm[k] = index of the k-th POI to visit (tile by tile, queue order inside a tile); tiles =
