@@ -75,7 +75,8 @@ typedef enum oc_hip_kind {
     OC_HIP_STRAIN = 9,
     OC_HIP_REGION_FIT = 10,
     OC_HIP_CALIBRATION = 11,
-    OC_HIP_STEREOVISION = 12
+    OC_HIP_STEREOVISION = 12,
+    OC_HIP_MATCHER = 13
 } oc_hip_kind;
 
 #define OC_HIP_POI2D_BYTES 100
@@ -423,6 +424,10 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     oc_hip_group_queue(engine, 0)); fails instead of falling back when librccl is unusable.  Exists
  *                     so that the RCCL binding (dlopen, version check, ncclCommInitAll, ncclAllGather) can be executed
  *                     on a one-GPU machine
+ *   "match_splits"    descriptor matcher only: parts the candidate range of the distance kernel is cut into; 0 (default) =
+ *                     automatic (enough parts for two workgroups per CU), 1 ... 64 forced.  Same bits for every value.  The
+ *                     matcher also takes "arith_fma" (see oc_hip_matcher_create); every other engine refuses this key with
+ *                     OC_HIP_ERR_UNSUPPORTED
  * A device group (oc_hip_set_devices) hands every key on to its members. */
 int oc_hip_set_tuning(oc_hip_engine* engine, const char* key, int value);
 
@@ -473,6 +478,40 @@ int oc_hip_compute_one_with_offset(oc_hip_engine* engine, void* poi, const float
 int oc_hip_set_self_adaptive(oc_hip_engine* engine, int enable);
 /* wait for everything enqueued on the engine's stream */
 int oc_hip_synchronize(oc_hip_engine* engine);
+
+/* ---- descriptor matching (SIFT3D's brute-force keypoint matching) --------- */
+/* The matching stage of SIFT3D::compute (src/oc_sift.cpp:625-674, 1251-1418, 1420-1487) for descriptors computed anywhere:
+ * rows of `dim` float32 (the reference's SIFT3D: 768; OpenCV's SIFT: 128).  `dim` is fixed at creation and must be a
+ * multiple of 32 in [32, 1024] (anything else: OC_HIP_ERR_INVALID).  The squared distance of a pair is the sequential
+ * float32 sum of :643-648 (acc = acc + d * d over k ascending; fmaf(d, d, acc) under oc_hip_set_tuning("arith_fma", 1)), so
+ * every result equals the reference's loop bit for bit.  The handle supports set_stream, synchronize, profile_* (the
+ * distance kernel), set_tuning ("arith_fma", "match_splits": 0 = automatic, 1 ... 64 = the number of parts the candidate
+ * range is cut into; results do not depend on it) and destroy.  Not supported (OC_HIP_ERR_UNSUPPORTED): oc_hip_set_devices
+ * with more than one device, oc_hip_compute*, oc_hip_set_images*.
+ * matching_ratio = SIFT3D::matching_ratio (:629); must be >= 0 and finite. */
+int oc_hip_matcher_create(int dim, float matching_ratio, int device, oc_hip_engine** out);
+/* SIFT3D::setMatchingRatio(float matching_ratio)  src/oc_sift.cpp:204-207 (default 0.85, :154) */
+int oc_hip_matcher_set_ratio(oc_hip_engine* engine, float matching_ratio);
+/* descriptor1 / descriptor2 of :625, :1251, :1420 as ONE row-major block rows[count][dim] (the reference's float** rows
+ * gathered).  side 0 = reference keypoints, 1 = target keypoints.  OC_HIP_HOST blocks are copied; OC_HIP_DEVICE blocks
+ * are used in place (16-byte aligned) until the side is set again.  A second call replaces the side.  count 0 is legal. */
+int oc_hip_matcher_set_descriptors(oc_hip_engine* engine, int side, const float* rows, size_t count, int memory);
+/* SIFT3D::bruteforceMatch (:625-674).  direction 0: every reference keypoint against all target keypoints, 1: the other
+ * way round.  matched_idx[i] = the nearest candidate when best < ratio^2 * second (:666), else -1 -- EVERY entry is written
+ * (the reference leaves failing entries as the caller initialised them); best_sq / second_sq (may be null): the two
+ * smallest squared distances under (distance, index), FLT_MAX where no candidate exists; *n_matched (may be null; a host
+ * variable, the call waits for the stream when it is given): the reference's return value.  The three arrays have one
+ * entry per query and live where `memory` says. */
+int oc_hip_matcher_nearest(oc_hip_engine* engine, int direction, int* matched_idx, float* best_sq, float* second_sq,
+                           size_t* n_matched, int memory);
+/* mode 0 = SIFT3D::monodirectionalMatch (:1251-1418): ratio test, then of the reference keypoints that chose the same
+ * target the one with the smallest (distance, index) stays when it passes the ratio test against the group's second
+ * (:1361-1387); pairs in descending target index.  mode 1 = SIFT3D::bidirectionalMatch (:1420-1487): pairs (i, r2t[i])
+ * with t2r[r2t[i]] == i in ascending i.  ref_idx / tar_idx: `capacity` entries each, where `memory` says; *n_pairs (host,
+ * required) receives the number of pairs.  capacity smaller than that: OC_HIP_ERR_INVALID, nothing is written and
+ * *n_pairs carries the needed size (min(count_ref, count_tar) always suffices).  The call waits for the stream. */
+int oc_hip_matcher_match(oc_hip_engine* engine, int mode, int* ref_idx, int* tar_idx, size_t capacity, size_t* n_pairs,
+                         int memory);
 
 /* ---- introspection (tests, bench, profiling) ------------------------------ */
 int oc_hip_get_kind(const oc_hip_engine* engine, int* kind);

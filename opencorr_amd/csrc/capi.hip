@@ -737,6 +737,7 @@ static int upload_image(oc_hip_engine* e, const float* src, size_t count, int me
 int oc_hip_set_images2d(oc_hip_engine* e, const float* ref, const float* tar, int height, int width, int layout,
                         int memory) {
     OC_ACTIVATE(e);
+    if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
     if (e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images2d called on a 3D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null image pointer");
     if (height < 5 || width < 5) return fail(OC_HIP_ERR_INVALID, "image too small: %d x %d", width, height);
@@ -776,6 +777,7 @@ int oc_hip_set_images2d(oc_hip_engine* e, const float* ref, const float* tar, in
 int oc_hip_set_images3d(oc_hip_engine* e, const float* ref, const float* tar, int dim_x, int dim_y, int dim_z,
                         int memory) {
     OC_ACTIVATE(e);
+    if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
     if (!e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images3d called on a 2D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null volume pointer");
     if (dim_x < 15 || dim_y < 15 || dim_z < 15)
@@ -878,8 +880,12 @@ static int rehome(oc_hip_engine* e, int device) {
     for (DevBuf* b : {&e->gx, &e->gy, &e->gz, &e->coef, &e->coef_gx, &e->coef_gy, &e->tmp, &e->poi_stage, &e->off_stage, &e->cursors,
                       &e->perm, &e->tiles, &e->perm_slots, &e->split_scratch, &e->split_tmp, &e->prefilter_tmp, &e->st_box, &e->st_counts, &e->st_start, &e->st_cursor, &e->st_slots,
                       &e->st_order, &e->st_recs, &e->st_fallback, &e->win, &e->freq, &e->norms, &e->flags, &e->group_mirror,
-                      &e->group_off_mirror, &e->setup_cache_recs, &e->setup_cache_xy, &e->setup_cache_word})
+                      &e->group_off_mirror, &e->setup_cache_recs, &e->setup_cache_xy, &e->setup_cache_word, &e->mt_desc[0], &e->mt_desc[1],
+                      &e->mt_idx[0], &e->mt_idx[1], &e->mt_best[0], &e->mt_best[1], &e->mt_second[0], &e->mt_second[1], &e->mt_part, &e->mt_keys,
+                      &e->mt_scan, &e->mt_pairs, &e->mt_counter})
         b->release();
+    e->mt_count[0] = e->mt_count[1] = 0;  // (descriptors are set again, like the images)
+    e->mt_ext[0] = e->mt_ext[1] = nullptr;
     e->setup_cache_valid = false;
     e->setup_cache_last = 0;
     e->img.reset();
@@ -916,6 +922,8 @@ int oc_hip_set_devices(oc_hip_engine* e, const int* device_ids, int n_devices) {
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Calibration / Stereovision handles stay on the device they were created for");
     if (n_devices > 1 && (e->kind == OC_HIP_STRAIN || e->kind == OC_HIP_REGION_FIT))
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Strain / RegionFit need every neighbour of a POI and stay on one device");
+    if (n_devices > 1 && e->is_matcher())
+        return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a descriptor matcher needs every candidate of a query and stays on one device");
     int ndev = 0;
     OC_HIP_TRY(hipGetDeviceCount(&ndev));
     for (int i = 0; i < n_devices; i++)
@@ -1090,9 +1098,14 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
     } else if (k == "icgn2d_xcd" || k == "xcd") {
         e->icgn2d_xcd = value != 0;
     } else if (k == "arith_fma") {
-        if (value != 0 && !(e->is_icgn2d() || e->kind == OC_HIP_ICGN3D1))
-            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines have a fused-arithmetic build");
+        if (value != 0 && !(e->is_icgn2d() || e->kind == OC_HIP_ICGN3D1 || e->is_matcher()))
+            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines and the descriptor matcher have a fused-arithmetic build");
         e->arith_fma = value != 0;
+    } else if (k == "match_splits") {
+        // parts the candidate range of the descriptor matcher's distance kernel is cut into (0 = automatic; same bits for every value)
+        if (!e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "match_splits: the key of the descriptor matcher");
+        if (value < 0 || value > ochip::kMatchMaxSplits) return fail(OC_HIP_ERR_INVALID, "match_splits must be 0 (automatic) ... %d", ochip::kMatchMaxSplits);
+        e->mt_splits = value;
     } else if (k == "arith_onepass") {
         if (value != 0 && e->kind == OC_HIP_ICGN3D1)
             return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass: the key of the ICGN2D1 / ICGN2D2 engines; the one-pass build of ICGN3D1 has a "
@@ -1256,6 +1269,7 @@ extern "C" {
 
 static int compute_impl(oc_hip_engine* e, void* pois, const float* offsets, size_t count, size_t stride_bytes, int memory) {
     OC_ACTIVATE(e);
+    if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
     if (count == 0) return OC_HIP_OK;
     if (!pois) return fail(OC_HIP_ERR_INVALID, "null POI buffer");
     if (stride_bytes < e->poi_bytes() || (stride_bytes & 3))
@@ -1299,6 +1313,8 @@ int oc_hip_compute_with_offsets(oc_hip_engine* e, void* pois, const float* cente
 int oc_hip_compute_chain(oc_hip_engine* const* engines, int n_engines, void* pois, size_t count, size_t stride_bytes, int memory) {
     if (!engines || n_engines < 1) return fail(OC_HIP_ERR_INVALID, "compute_chain: need at least one engine");
     for (int i = 0; i < n_engines; i++) OC_TRY(check_engine(engines[i]));
+    for (int i = 0; i < n_engines; i++)
+        if (engines[i]->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: a descriptor matcher has no POI queue");
     if (n_engines == 1) return compute_impl(engines[0], pois, nullptr, count, stride_bytes, memory);
     oc_hip_engine* lead = engines[0];
     for (int i = 1; i < n_engines; i++) {
@@ -1421,6 +1437,7 @@ static void serve_single_batch(oc_hip_engine* e, std::vector<oc_hip_engine::Sing
 // (host/single_combiner.h: the protocol and its invariants).  A POI's result does not depend on the batch it travels in (the
 // per-POI solves are independent: tests/test_gpu_parity_2d.py::test_host_pipeline_chunks_change_no_bits).
 static int compute_single(oc_hip_engine* e, void* poi, const float* offset) {
+    if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
     if (!poi) return fail(OC_HIP_ERR_INVALID, "null POI");
     if (!e->single_combine) return compute_impl(e, poi, offset, 1, e->poi_bytes(), OC_HIP_HOST);
     oc_hip_engine::SingleCombiner::Request req(poi, offset);

@@ -230,6 +230,14 @@ struct oc_hip_engine {
     DevBuf cal_map_x, cal_map_y, cal_stage;
     oc_hip_engine* stereo_cam[2] = {nullptr, nullptr};
     float stereo_F[9] = {};
+    // Descriptor matcher (capi_match.hip; SIFT3D::bruteforceMatch and the two match modes, src/oc_sift.cpp:625-674, 1251-1487):
+    // side 0 = reference, 1 = target.  HOST descriptors are copied into mt_desc, DEVICE ones are used in place (mt_ext).
+    int mt_dim = 0, mt_splits = 0;   // "match_splits" tuning key: 0 = automatic, 1 ... 64 forced
+    float mt_ratio = 0.f;
+    size_t mt_count[2] = {0, 0};
+    const float* mt_ext[2] = {nullptr, nullptr};
+    DevBuf mt_desc[2], mt_idx[2], mt_best[2], mt_second[2];   // [direction] for the results: 0 = ref -> tar, 1 = tar -> ref
+    DevBuf mt_part, mt_keys, mt_scan, mt_pairs, mt_counter;
     float lm_lambda = 100.f, lm_alpha = 0.1f, lm_beta = 10.f;  // DampingParameter defaults, src/oc_iclm.h:33-38
     int icgn2d_tile_px = 128;  // 0 = visit the queue in its own order (64 until round 3; 128 suits the lockstep sweeps: 3.29 vs 3.34 ms)
     // FFTCC working set
@@ -297,6 +305,7 @@ struct oc_hip_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     mutable std::mutex mu;
 
+    bool is_matcher() const { return kind == OC_HIP_MATCHER; }
     bool is3d() const { return kind == OC_HIP_FFTCC3D || kind == OC_HIP_ICGN3D1; }
     bool is_iclm() const { return kind == OC_HIP_ICLM2D1 || kind == OC_HIP_ICLM2D2; }
     bool is_icgn2d() const { return kind == OC_HIP_ICGN2D1 || kind == OC_HIP_ICGN2D2 || is_iclm(); }

@@ -367,5 +367,33 @@ size_t poi_split_scratch_words(size_t count);
 hipError_t launch_poi_split(const float* pois, int stride_floats, size_t count, const PoiSplitParams& p, const unsigned* index_in,
                             float* out0, size_t out0_offset, unsigned* index_out0, float* out1, unsigned* index_out,
                             float* main_queue, size_t main_count, unsigned* scratch, hipStream_t stream);
+// the partitions' exclusive scan on its own: block_counts[2 * b + k] -> exclusive prefix over b, in place; totals[k] = the sums
+hipError_t launch_block_count_scan(unsigned* block_counts, size_t nblocks, unsigned* totals, hipStream_t stream);
+
+// ---- match.hip --------------------------------------------------------------
+// brute-force descriptor matching (SIFT3D::bruteforceMatch / monodirectionalMatch / bidirectionalMatch, src/oc_sift.cpp:625-674,
+// 1251-1418, 1420-1487): squared distances as sequential float32 sums over k, the two nearest candidates of every query under
+// (distance, index), the ratio test, and the two pair selections.  A partial is { bits(d0), j0, bits(d1), j1 }.
+constexpr int kMatchTile = 64;       // queries per workgroup and candidates per tile
+constexpr int kMatchMaxSplits = 64;
+bool match_dim_supported(int dim);   // a multiple of 32 in [32, 1024]
+// the candidate range cut into `splits` parts (gridDim.y); partials: splits * n_query records of 16 bytes
+hipError_t launch_match_top2(const float* query, size_t n_query, const float* cand, size_t n_cand, int dim, int splits, bool fma,
+                             void* partials, hipStream_t stream);
+// merges the parts, applies best < ratio_sq * second, writes every entry of matched_idx (-1 = no match), best, second and adds
+// the number of matches to *counter
+hipError_t launch_match_finalize(const void* partials, size_t n_query, int splits, float ratio_sq, int* matched_idx, float* best,
+                                 float* second, unsigned* counter, hipStream_t stream);
+// mode 0 (monodirectional): keys = 2 * n_tar 64-bit slots; the two rounds of atomicMin over the accepted reference keypoints
+hipError_t launch_match_many_to_one(const int* r2t, const float* best, size_t n_ref, size_t n_tar, unsigned long long* keys,
+                                    hipStream_t stream);
+// the surviving pairs in output order (mode 0: descending target index, mode 1: ascending reference index).  Words of scratch:
+size_t match_pairs_scratch_words(size_t n_ref, size_t n_tar, int mode);
+// count: per-block counts + scan, scratch's last-but-one two words are the totals (total pairs = the first of them)
+hipError_t launch_match_pairs_count(int mode, const int* r2t, const int* t2r, const unsigned long long* keys, size_t n_ref, size_t n_tar,
+                                    float ratio_sq, unsigned* scratch, hipStream_t stream);
+hipError_t launch_match_pairs_scatter(int mode, const int* r2t, const int* t2r, const unsigned long long* keys, size_t n_ref,
+                                      size_t n_tar, float ratio_sq, const unsigned* scratch, int* ref_idx, int* tar_idx,
+                                      hipStream_t stream);
 
 }  // namespace ochip

@@ -155,6 +155,15 @@ hipError_t launch_poi_index_range(const unsigned* index, size_t n, size_t limit,
     return hipGetLastError();
 }
 
+// The exclusive scan of the partitions above, for other order-preserving compactions (match.hip: the surviving keypoint pairs):
+// block_counts holds two counts per block (a user of one class leaves the second count 0), totals two words.
+hipError_t launch_block_count_scan(unsigned* block_counts, size_t nblocks, unsigned* totals, hipStream_t stream) {
+    if (nblocks == 0 || nblocks > 0x7fffffffull) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(poi_split_scan_kernel, dim3(1), dim3(1024), 0, stream, block_counts, (unsigned)nblocks, totals);
+    return hipGetLastError();
+}
+
 // per-block counts (2 per block) | totals[2] | bad-index flag
 size_t poi_split_scratch_words(size_t count) { return 2 * ((count + kSplitBlock - 1) / kSplitBlock) + 3; }
 

@@ -726,6 +726,78 @@ class Stereovision(_Handle):
         return pois
 
 
+class DescriptorMatcher(_Handle):
+    """DescriptorMatcher(dim, ratio) -- the matching stage of SIFT3D (src/oc_sift.cpp:625-674, 1251-1418, 1420-1487) for
+    descriptors computed anywhere: rows of ``dim`` float32 (a multiple of 32 in [32, 1024]; SIFT3D 768, OpenCV's SIFT 128).
+    Squared distances are the reference's sequential float32 sums, so the results equal its loops bit for bit
+    (``set_tuning("arith_fma", 1)``: the sums a ``-mfma`` build of the reference forms).  NumPy descriptors are copied, CUDA
+    torch tensors are used in place; results come back as NumPy arrays unless both sides are CUDA tensors."""
+
+    MONODIRECTIONAL, BIDIRECTIONAL = 0, 1
+
+    def __init__(self, dim, ratio=0.85, device=0):
+        super().__init__(device)
+        self._dim = int(dim)
+        self._side = [None, None]
+        self._count = [0, 0]
+        capi.check(capi.lib().oc_hip_matcher_create(self._dim, float(ratio), int(device), ctypes.byref(self._h)))
+
+    def set_ratio(self, ratio):
+        capi.check(capi.lib().oc_hip_matcher_set_ratio(self._h, float(ratio)))
+
+    def set_tuning(self, key, value):
+        """``"arith_fma"`` (0 / 1) and ``"match_splits"`` (0 = automatic, 1 ... 64 parts of the candidate range; same bits)."""
+        capi.check(capi.lib().oc_hip_set_tuning(self._h, key.encode(), int(value)))
+
+    def set_descriptors(self, side, rows):
+        """``side`` 0 = reference, 1 = target keypoints; ``rows``: (count, dim) float32.  A second call replaces the side."""
+        if side not in (0, 1):
+            raise ValueError("side must be 0 (reference) or 1 (target)")
+        if not _is_torch(rows):
+            rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if len(rows.shape) != 2 or rows.shape[1] != self._dim:
+            raise ValueError("descriptors must have shape (count, %d)" % self._dim)
+        self._adopt_stream_of(rows)
+        ptr, mem, keep = _buf(rows)
+        capi.check(capi.lib().oc_hip_matcher_set_descriptors(self._h, side, ptr, rows.shape[0], mem))
+        self._side[side] = keep if mem == capi.DEVICE else None   # a device block is used in place: keep it alive
+        self._count[side] = int(rows.shape[0])
+
+    def _on_device(self):
+        return self._side[0] is not None and self._side[1] is not None
+
+    def _out(self, n, dtype):
+        """(array or tensor, pointer) of n entries where the results go"""
+        if self._on_device():
+            import torch
+            t = torch.empty(n, dtype=torch.int32 if dtype == np.int32 else torch.float32, device=self._side[0].device)
+            return t, ctypes.c_void_p(t.data_ptr())
+        a = np.empty(n, dtype=dtype)
+        return a, ctypes.c_void_p(a.ctypes.data)
+
+    def nearest(self, direction=0):
+        """SIFT3D::bruteforceMatch: (matched_idx, best_sq, second_sq), one entry per query; direction 0 = ref -> tar,
+        1 = tar -> ref.  matched_idx is -1 where the ratio test fails."""
+        n = self._count[0 if direction == 0 else 1]
+        mem = capi.DEVICE if self._on_device() else capi.HOST
+        idx, pi = self._out(n, np.int32)
+        best, pb = self._out(n, np.float32)
+        second, ps = self._out(n, np.float32)
+        capi.check(capi.lib().oc_hip_matcher_nearest(self._h, int(direction), pi, pb, ps, None, mem))
+        return idx, best, second
+
+    def match(self, mode=0):
+        """mode 0 = SIFT3D::monodirectionalMatch (pairs in descending target index), 1 = SIFT3D::bidirectionalMatch (ascending
+        reference index): (ref_idx, tar_idx)."""
+        cap = min(self._count)
+        mem = capi.DEVICE if self._on_device() else capi.HOST
+        ref, pr = self._out(cap, np.int32)
+        tar, pt = self._out(cap, np.int32)
+        n = ctypes.c_size_t()
+        capi.check(capi.lib().oc_hip_matcher_match(self._h, int(mode), pr, pt, cap, ctypes.byref(n), mem))
+        return ref[:n.value], tar[:n.value]
+
+
 class RegionFit:
     """RegionFit2D / RegionFit3D(neighbor_search_radius, neighbor_number_min, thread_number) -- src/oc_region_fit.h.
 
