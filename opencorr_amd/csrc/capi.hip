@@ -4,6 +4,7 @@
 // POI staging, rocFFT plans, stream and profiling events.  No CPU compute path
 // exists here: every compute call ends in HIP kernel launches or fails.
 #include "capi_internal.h"
+#include "host/icgn2d_plan.h"
 
 namespace ochip_capi {
 
@@ -205,6 +206,29 @@ int check_image2d_limits(const char* who, const ImagePair& im, unsigned long lon
 // ---------------------------------------------------------------------------
 // ICGN2D
 // ---------------------------------------------------------------------------
+// a refusal of host/icgn2d_plan.h in words (OC_HIP_OK: the plan is none)
+int icgn2d_refusal(const ochip_host::Icgn2dRequest& q, const ochip_host::Icgn2dPlan& plan) {
+    using ochip_host::Icgn2dRefusal;
+    const int which = q.dof == 6 ? 1 : 2, w = 2 * q.rx + 1, h = 2 * q.ry + 1;
+    const long long N = ochip_host::icgn2d_samples(q.rx, q.ry);
+    switch (plan.refusal) {
+        case Icgn2dRefusal::None: break;
+        case Icgn2dRefusal::OnePassOffsets:
+            return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: centre offsets are not supported under arith_onepass = 1 (the one-pass kernel keeps "
+                                                "integer local coordinates in a per-workgroup table); set arith_onepass = 0 for this call", which);
+        case Icgn2dRefusal::OnePassSelfAdaptive:
+            return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: self-adaptive subset radii are not supported under arith_onepass = 1 (the one-pass "
+                                                "kernel runs one radius per launch); set arith_onepass = 0", which);
+        case Icgn2dRefusal::OnePassTooLarge:
+            return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: subset %dx%d (%lld samples) exceeds the one-pass kernel's on-chip limit of %d samples",
+                        which, w, h, N, plan.limit);
+        case Icgn2dRefusal::TooLarge:
+            return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: subset %dx%d (%lld samples) exceeds the on-chip limit of %d samples", which, w, h, N,
+                        plan.limit);
+    }
+    return OC_HIP_OK;
+}
+
 int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, const float* d_offsets) {
     if (!e->img || e->img->ndim != 2) return fail(OC_HIP_ERR_INVALID, "ICGN2D: set_images2d has not been called");
     if (!e->ref_ready || !e->tar_ready)
@@ -213,15 +237,11 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
     OC_TRY(check_image2d_limits("ICGN2D", im, 1ull << 28));
     const int dof = (e->kind == OC_HIP_ICGN2D1 || e->kind == OC_HIP_ICLM2D1) ? 6 : 12;
     const bool lm = e->is_iclm();
-    // the one-pass arithmetic contract (icgn2d_onepass.hip): one radius per launch, integer local coordinates -- what it does not
-    // support is refused, never run under another contract
-    const bool onepass = e->arith_onepass && !lm;
-    if (onepass && d_offsets)
-        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: centre offsets are not supported under arith_onepass = 1 (the one-pass kernel keeps "
-                                            "integer local coordinates in a per-workgroup table); set arith_onepass = 0 for this call", dof == 6 ? 1 : 2);
-    if (onepass && e->self_adaptive)
-        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: self-adaptive subset radii are not supported under arith_onepass = 1 (the one-pass "
-                                            "kernel runs one radius per launch); set arith_onepass = 0", dof == 6 ? 1 : 2);
+    // what the call brings, for the rules of host/icgn2d_plan.h (in the order of Icgn2dRequest's fields)
+    ochip_host::Icgn2dRequest req = {dof, lm, e->arith_onepass != 0, e->self_adaptive != 0, d_offsets != nullptr, e->icgn2d_variant, e->rx, e->ry,
+                                     count, e->icgn2d_setup_cache != 0, e->icgn2d_split_chunks, OC_BUILD_AB != 0, false};
+    // (refused before any device work: what the one-pass contract does not support, whatever the radii)
+    OC_TRY(icgn2d_refusal(req, {ochip_host::icgn2d_refused_before_radii(req)}));
     int rx = e->rx, ry = e->ry;
     if (e->self_adaptive) {
         // every POI brings its own radius (src/oc_icgn.cpp:152-158): size the on-chip arrays for the largest
@@ -242,75 +262,26 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
                              e->lm_alpha,  e->lm_beta,         e->arith_fma,      nullptr};
     // the value plane behind the target table (oc_hip_prepare_tar): sweeps of integer-translation warps read it ("icgn2d_int_first")
     P.lut_val = (e->icgn2d_int_first && e->tar_ready && e->coef_has_val) ? e->coef.as<float>() + im.count() * 16 : nullptr;
-    const long long N = (2LL * rx + 1) * (2LL * ry + 1);
-    // fall back to the LDS-light single-wave variant when the tuned one cannot hold the subset
-    int variant = e->icgn2d_variant;
-    // Variants 10 / 11 (4-wave lockstep workgroups on the compact coordinate table, six / four per CU): one radius per launch, 8-bit
-    // column and row indices, every one of those workgroups inside a CU's LDS -- a launch that is not all of that takes the
-    // automatic choice below instead, silently and with the same bits (which takes them for queues >= 32768 POIs only)
-    const bool compact_ok = !lm && !e->self_adaptive;
-    if ((variant == 10 || variant == 11) && !(compact_ok && ochip::icgn2d_compact_fits(variant, rx, ry))) variant = -1;
-    const bool chosen = variant < 0;
-    if (variant < 0) {
-        // ICGN2D1: the coordinate-table variant at 6 waves per SIMD while three of its workgroups fit a CU's LDS (subsets up
-        // to 19 passes of 64 samples, i.e. 35 x 34), the LDS-light 4-wave workgroups beyond; ICGN2D2: see below
-        // (queues that fill the chip only a couple of times over finish sooner in the finer-grained 4-wave workgroups:
-        // config A, 10 000 POIs, 0.33 against 0.38 ms)
-        const long long passes = ((2LL * rx + 1) * (2LL * ry + 1) + 63) / 64;
-        // ICGN2D2: the table variant in 8-wave workgroups while two of them fit a CU (up to 28 passes: 41 x 41), measured
-        // 3.65 against 3.81 ms on config C (profiles/r03q_icgn2d2_variant_ab_configC.json)
-        variant = dof == 12 ? (passes <= 28 && count >= 32768 ? 4 : 3) : (passes <= 19 && count >= 32768 ? 5 : 2);
-        // ... and in their place, where they are admissible, the same sweeps in 4-wave workgroups on the compact table, six /
-        // four per CU: interleaved on MI355X (profiles/r11a_icgn2d_4wave_compact_table_ab.json) config B 2.49 against 2.59 ms
-        // and config C 2.30 against 2.42 ms per launch served by the set-up cache, 2.86 / 2.91 and 3.25 / 3.41 without it
-        constexpr bool kCompactDefault[2] = {true, true};   // [0] ICGN2D1: 10 for 5, [1] ICGN2D2: 11 for 4
-        const int compact = dof == 12 ? 11 : 10;
-        if ((variant == 4 || variant == 5) && kCompactDefault[dof == 12] && compact_ok &&
-            ochip::icgn2d_compact_admissible(compact, rx, ry, count))
-            variant = compact;
-    }
-    // per-POI radii: no shared coordinate table, and the per-wave arrays are sized for the LARGEST subset of the batch -- the
-    // target-array-only shape (variant 7) keeps four workgroups on a CU where variant 2 holds two (bench.py paths_8f_row1)
-    // -- when variant 2's two arrays per wave would leave a CU at most two workgroups (subsets from 26 passes = 41 x 40 up: the
-    // measured case, radii 12 ... 20: 4.91 -> 3.98 ms); smaller batches keep variant 2, which is 4 % ahead at equal occupancy
-    // (3.49 vs 3.61 ms on a uniform r = 16: one image read per sample fewer).  ADVICE r5.
-    if (e->self_adaptive && (chosen || ochip::icgn2d_variant_uses_table(variant))) {
-        const long long passes_sa = (N + 63) / 64;
-        const bool crowded = 3 * (2 * 4 * passes_sa * 256) > (160 * 1024 - 2048);   // three workgroups of variant 2 no longer fit
-        variant = crowded ? 7 : (dof == 12 ? 3 : 2);
-    }
-    if (lm) variant = 1;  // the IC-LM launch shape has the LDS footprint of variant 1
-    // variant 9 = icgn2d_band.hip (A/B build only: the workgroup's band of the table staged in LDS, the warped subset in registers --
-    // bit-exact, measured 1.7 x slower than variant 5): one radius per launch and at most the passes it unrolls
+    // which variant on which launch path, with or without the set-up cache -- or nothing at all
+    req.rx = rx;
+    req.ry = ry;
 #if OC_BUILD_AB
-    const bool band = variant == 9 && !lm && !e->self_adaptive && ochip::icgn2d_band_supported(dof, rx, ry);
-#else
-    const bool band = false;
+    req.band_supported = ochip::icgn2d_band_supported(dof, rx, ry);
 #endif
-    if (variant == 9 && !band) variant = dof == 12 ? 3 : 2;
-    if (onepass && N > ochip::icgn2d_onepass_max_samples())
-        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: subset %dx%d (%lld samples) exceeds the one-pass kernel's on-chip limit of %d samples",
-                    dof == 6 ? 1 : 2, 2 * rx + 1, 2 * ry + 1, N, ochip::icgn2d_onepass_max_samples());
-    if (onepass) variant = dof == 6 ? 5 : 4;   // (one launch shape, its own kernel: the variant no longer matters below)
-    if (!band && !onepass && N > ochip::icgn2d_max_samples(variant)) variant = 1;
-    if (!band && !onepass && N > ochip::icgn2d_max_samples(variant))
-        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN2D%d: subset %dx%d (%lld samples) exceeds the on-chip limit of %d samples",
-                    dof == 6 ? 1 : 2, 2 * rx + 1, 2 * ry + 1, N, ochip::icgn2d_max_samples(variant));
-    if (variant == 8 && !lm) {
+    const ochip_host::Icgn2dPlan plan = ochip_host::icgn2d_plan(req);
+    OC_TRY(icgn2d_refusal(req, plan));
+    using ochip_host::Icgn2dPath;
+    if (plan.needs_setup_records) {
         OC_TRY(e->setup_recs.reserve(count * (size_t)ochip::icgn2d_setup_record_floats(dof) * sizeof(float)));
         P.setup = e->setup_recs.as<float>();
     }
-    // one wave per POI; grid.x is limited to 2^31-1
-    const size_t kMaxGrid = 1u << 30;
+    const size_t kMaxGrid = ochip_host::kIcgn2dMaxGrid;
     // Set-up cache: the big-queue table variants keep { reference mean, norm, H^-1 } per POI from call to call (icgn2d.hip CACHE).
     // A sequence that correlates many targets against one reference over one grid -- overwrite the target, prepare_tar(),
     // compute() -- pays for the set-up once.  The host decides what it can know (the key); whether the queue still holds the
-    // coordinates the records were built for is decided on the device by the check in front of the launch.  Centre offsets,
-    // self-adaptive radii, IC-LM and the small-queue variants go around it.
+    // coordinates the records were built for is decided on the device by the check in front of the launch.
     e->setup_cache_last = 0;
-    const bool cached = e->icgn2d_setup_cache && !onepass && !lm && !band && !d_offsets && !e->self_adaptive &&
-                        (variant == 4 || variant == 5 || variant == 10 || variant == 11) &&
-                        count <= kMaxGrid;
+    const bool cached = plan.uses_setup_cache;
     oc_hip_engine::SetupCacheKey cache_key;
     bool cache_hit = false;
     unsigned *cache_xy = nullptr, *cache_word = nullptr;
@@ -325,7 +296,7 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
         }
         cache_key.count = count;
         cache_key.stride_f = stride_f;
-        cache_key.variant = variant;
+        cache_key.variant = plan.variant;
         cache_key.dof = dof;
         cache_key.rx = rx;
         cache_key.ry = ry;
@@ -354,7 +325,7 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
         OC_TRY(tile_order(e, pois, stride_f, n, &P.perm, cache_xy, cache_word, P.cache_epoch));
         ProfScope prof(e);  // the solver kernel alone (what rocprofv3 reports for it)
         hipError_t err;
-        if (variant == 8 && !lm && e->icgn2d_split_chunks >= 2 && n >= 16384) {
+        if (plan.path == Icgn2dPath::SplitPipelined && n >= ochip_host::kIcgn2dSplitMinPois) {
             // the split launch shape as a two-stream pipeline over chunks of the visiting order: set-up kernel of chunk c on
             // the auxiliary stream (at most two chunks ahead), iteration kernel of chunk c on the engine's stream behind it
             const size_t C = (size_t)e->icgn2d_split_chunks;
@@ -392,20 +363,20 @@ int run_icgn2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, cons
             }
             continue;
         }
-        if (onepass)
+        if (plan.path == Icgn2dPath::OnePass)
             err = dof == 6 ? ochip::launch_icgn2d1_onepass(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream)
                            : ochip::launch_icgn2d2_onepass(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream);
-        else if (lm)
+        else if (plan.path == Icgn2dPath::Lm)
             err = dof == 6 ? ochip::launch_iclm2d1(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream)
                            : ochip::launch_iclm2d2(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream);
 #if OC_BUILD_AB
-        else if (band)
+        else if (plan.path == Icgn2dPath::Band)
             err = dof == 6 ? ochip::launch_icgn2d1_band(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream)
                            : ochip::launch_icgn2d2_band(P, pois, stride_f, n, e->icgn2d_xcd != 0, e->stream);
 #endif
         else
-            err = dof == 6 ? ochip::launch_icgn2d1(P, pois, stride_f, n, variant, e->icgn2d_xcd != 0, e->stream)
-                           : ochip::launch_icgn2d2(P, pois, stride_f, n, variant, e->icgn2d_xcd != 0, e->stream);
+            err = dof == 6 ? ochip::launch_icgn2d1(P, pois, stride_f, n, plan.variant, e->icgn2d_xcd != 0, e->stream)
+                           : ochip::launch_icgn2d2(P, pois, stride_f, n, plan.variant, e->icgn2d_xcd != 0, e->stream);
         if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "ICGN2D kernel launch failed: %s", hipGetErrorString(err));
     }
     if (cached) {
@@ -1089,9 +1060,9 @@ int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
     std::lock_guard<std::mutex> lock(e->mu);
     const std::string k(key);
     if (k == "icgn2d_variant") {
-        if (value < -1 || value >= ochip::icgn2d_variant_count())
-            return fail(OC_HIP_ERR_INVALID, "icgn2d_variant %d out of range [-1 (automatic), %d)", value, ochip::icgn2d_variant_count());
-        if (value >= 0 && !ochip::icgn2d_variant_built(value))
+        if (value < -1 || value >= ochip_host::kIcgn2dVariantCount)
+            return fail(OC_HIP_ERR_INVALID, "icgn2d_variant %d out of range [-1 (automatic), %d)", value, ochip_host::kIcgn2dVariantCount);
+        if (value >= 0 && !ochip_host::icgn2d_variant_built(value, OC_BUILD_AB != 0))
             return fail(OC_HIP_ERR_UNSUPPORTED, "icgn2d_variant %d is an A/B partner that only the A/B build of the library contains "
                                                "(python -m opencorr_amd.build --ab)", value);
         e->icgn2d_variant = value;
@@ -1598,10 +1569,11 @@ int oc_hip_icgn2d_setup_cache_last(oc_hip_engine* e, int* state) {
 
 int oc_hip_icgn2d_variant_limits(int variant, int radius_x, int radius_y, size_t count, int* max_samples, int* compact_admissible) {
     if (!max_samples || !compact_admissible) return fail(OC_HIP_ERR_INVALID, "null argument");
-    if (variant < 0 || variant >= ochip::icgn2d_variant_count())
-        return fail(OC_HIP_ERR_INVALID, "icgn2d_variant %d out of range [0, %d)", variant, ochip::icgn2d_variant_count());
-    *max_samples = ochip::icgn2d_max_samples(variant);
-    *compact_admissible = ochip::icgn2d_compact_admissible(variant, radius_x, radius_y, count) ? 2 : ochip::icgn2d_compact_fits(variant, radius_x, radius_y) ? 1 : 0;
+    if (variant < 0 || variant >= ochip_host::kIcgn2dVariantCount)
+        return fail(OC_HIP_ERR_INVALID, "icgn2d_variant %d out of range [0, %d)", variant, ochip_host::kIcgn2dVariantCount);
+    *max_samples = ochip_host::icgn2d_max_samples(variant);
+    // (2: the automatic choice takes it, which needs a big queue as well; 1: it runs when named)
+    *compact_admissible = !ochip_host::icgn2d_compact_fits(variant, radius_x, radius_y) ? 0 : count >= ochip_host::kIcgn2dBigQueue ? 2 : 1;
     return OC_HIP_OK;
 }
 

@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "dic2d_device.h"
+#include "host/icgn2d_plan.h"  // the variant table (and OC_V5_G / OC_V5_OCC, the A/B sweep's knobs of variant 5), the LDS formula
 #include "oc_kernels.h"
 // OC_ABLATE2D (experiments only, tools/ablate_icgn2d.sh; the shipped library is built without it): 1 = every POI runs
 // exactly three iterations (no convergence test, no abort) so that builds can be compared; 2 = from the second iteration
@@ -84,13 +85,6 @@
 #endif
 #ifndef OC_NUM_BATCH
 #define OC_NUM_BATCH 6
-#endif
-// gathers in flight and register budget (waves per SIMD) of variant 5 (experiments: tools/ab_build.py)
-#ifndef OC_V5_G
-#define OC_V5_G 2
-#endif
-#ifndef OC_V5_OCC
-#define OC_V5_OCC 6
 #endif
 #ifndef OC_UNIFORM_IN_VGPR
 #define OC_UNIFORM_IN_VGPR 0
@@ -1187,24 +1181,18 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
 // oc_hip_set_tuning("icgn2d_variant", i) / ("icgn2d_xcd", 0|1); defaults chosen from the
 // MI355X sweep in DESIGN.md section 4.
 // ---------------------------------------------------------------------------
-constexpr int kLdsBudget = 160 * 1024 - 2048;  // dynamic LDS; 2 KB stay free for the static area of the cooperative inverse
-
-struct VariantInfo {
-    int g, mode, pipe, wpb, occ;
-};
+using ochip_host::kIcgn2dLdsBudget;
 
 template <int DOF, int G, int MODE, int PIPE, int WPB, int OCC, int OFFS, int LM = 0, int PHASE = 0>
 static hipError_t launch_t(const Icgn2dParams& p, float* pois, int stride_f, size_t count, int nt, bool xcd,
                            hipStream_t stream) {
-    constexpr int arrays = PHASE == 1 ? 0 : (MODE == 0 ? 4 : ((MODE == 4 || MODE == 6 || MODE == 2) ? 1 : 2));  // (the set-up kernel: table only)
-    // (in half floats per sample slot: the table takes 3 floats, the compact one of MODE 6 a float and a half)
-    size_t lds = ((size_t)2 * arrays * WPB + (MODE == 6 ? 3 : MODE >= 3 ? 6 : 0)) * nt * kWave * (sizeof(float) / 2);
-    if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+    size_t lds = ochip_host::icgn2d_lds_bytes(MODE, WPB, (size_t)nt, PHASE);
+    if (lds > (size_t)kIcgn2dLdsBudget) return hipErrorInvalidValue;
 #if OC_BUILD_AB
     // experiments only, A/B build only (tools/icgn2d_occupancy_probe.py): OC_ICGN2D_LDS_PAD=<bytes> raises the workgroup's LDS
     // request, i.e. lowers the number of workgroups a CU holds, with nothing else changed
     static const size_t lds_pad = std::getenv("OC_ICGN2D_LDS_PAD") ? (size_t)std::atol(std::getenv("OC_ICGN2D_LDS_PAD")) : 0;
-    if (lds_pad && lds_pad <= (size_t)kLdsBudget && lds_pad > lds) lds = lds_pad;
+    if (lds_pad && lds_pad <= (size_t)kIcgn2dLdsBudget && lds_pad > lds) lds = lds_pad;
 #endif
     if (PHASE != 0 && !p.setup) return hipErrorInvalidValue;
     auto kern = icgn2d_kernel<DOF, G, MODE, PIPE, WPB, OCC, OFFS, LM, PHASE>;
@@ -1217,7 +1205,7 @@ static hipError_t launch_t(const Icgn2dParams& p, float* pois, int stride_f, siz
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, kIcgn2dLdsBudget);
         if (err != hipSuccess) return err;
         attr_devices.fetch_or(bit, std::memory_order_release);
     }
@@ -1246,31 +1234,16 @@ static hipError_t launch_t(const Icgn2dParams& p, float* pois, int stride_f, siz
 //    whose largest subset is 41 x 41 still runs four 4-wave workgroups per CU instead of two.
 //    10, 11: variant 6's 4-wave lockstep workgroups on the compact table (MODE 6): six per CU at 80 VGPRs for ICGN2D1 (the
 //    24 waves of variant 5 as six independent workgroups instead of three), four per CU at 128 VGPRs for ICGN2D2; both use the
-//    set-up cache.  capi.hip admits them for subsets of at most 256 x 256 whose workgroups all fit a CU.
+//    set-up cache.  host/icgn2d_plan.h admits them for subsets of at most 256 x 256 whose workgroups all fit a CU.
 // Round 1's G = 2 and software-pipelined variants never won a sweep and are gone.
 // Variants 0, 6 and 8 are measured losers kept as A/B partners: they are compiled only into the A/B build of the library
 // (-DOC_BUILD_AB=1, opencorr_amd/build.py build_ab(); tests that compare them load that build).
-//        id  G mode pipe wpb occ
-#define OC_ICGN2D_VARIANTS_PRODUCT(X) \
-    X(1, 3, 1, 0, 1, 4)       \
-    X(2, 3, 1, 0, 4, 4)       \
-    X(3, 4, 1, 0, 1, 3)       \
-    X(4, 3, 4, 0, 8, 4)       \
-    X(5, OC_V5_G, 4, 0, 8, OC_V5_OCC) \
-    X(7, 3, 2, 0, 4, 4)       \
-    X(10, 2, 6, 0, 4, 6)      \
-    X(11, 3, 6, 0, 4, 4)
-#define OC_ICGN2D_VARIANTS_AB(X) \
-    X(0, 3, 0, 0, 1, 1)       \
-    X(6, 2, 4, 0, 4, 4)
+// The table itself (id, G, mode, pipe, wpb, occ per row) is host/icgn2d_plan.h's; the kernels of this build:
 #if OC_BUILD_AB
 #define OC_ICGN2D_VARIANTS(X) OC_ICGN2D_VARIANTS_PRODUCT(X) OC_ICGN2D_VARIANTS_AB(X)
 #else
 #define OC_ICGN2D_VARIANTS(X) OC_ICGN2D_VARIANTS_PRODUCT(X)
 #endif
-#define OC_ICGN2D_VARIANTS_ALL(X) OC_ICGN2D_VARIANTS_PRODUCT(X) OC_ICGN2D_VARIANTS_AB(X)
-
-constexpr int kSplitVariant = 8;
 
 template <int DOF>
 static hipError_t launch_dof(const Icgn2dParams& p, float* pois, int stride_f, size_t count, int variant, bool xcd,
@@ -1287,7 +1260,7 @@ static hipError_t launch_dof(const Icgn2dParams& p, float* pois, int stride_f, s
         OC_ICGN2D_VARIANTS(X)
 #undef X
 #if OC_BUILD_AB
-        case kSplitVariant: {
+        case 8: {
             // the split launch shape: the set-up kernel (table only in LDS, 8 / 4 waves per SIMD by registers) files
             // mean, norm and H^-1 per POI in p.setup, the iteration kernel -- the big-queue default's shape, variant 5 for
             // 6 DoF and variant 4 for 12 -- reads them.  Back to back on one stream here; capi.hip may instead feed the two
@@ -1339,62 +1312,7 @@ hipError_t launch_iclm2d2(const Icgn2dParams& p, float* pois, int stride_f, size
 
 #if !OC_FMA
 // ---- the arithmetic-independent part and the dispatch between the two builds (this translation unit only) ----
-using OC_ARITH::kLdsBudget;
-constexpr int kIcgn2dVariants = 12;  // 0 ... 7: one kernel each; 8: the split launch shape (set-up kernel + iteration kernel);
-                                     // 9: the band kernel of icgn2d_band.hip (capi.hip launches it; listed here for the tuning key);
-                                     // 10, 11: 4-wave lockstep workgroups on the compact table (MODE 6), six / four per CU
-
-int icgn2d_variant_count() { return kIcgn2dVariants; }
-
-// the launch shape of a variant id, whether this build contains it or not
-int icgn2d_variant_info(int variant, int* g, int* mode, int* pipe, int* wpb, int* occ) {
-    switch (variant) {
-#define X(ID, GG, MM, PP, WW, OO) \
-    case ID: *g = GG; *mode = MM; *pipe = PP; *wpb = WW; *occ = OO; return 0;
-        OC_ICGN2D_VARIANTS_ALL(X)
-#undef X
-        case 8: *g = OC_V5_G; *mode = 4; *pipe = 0; *wpb = 8; *occ = OC_V5_OCC; return 0;  // (the iteration kernel's shape at 6 DoF)
-        case 9: *g = 1; *mode = 5; *pipe = 0; *wpb = 8; *occ = 6; return 0;  // icgn2d_band.hip: table + LDS band, subset in registers
-        default: return -1;
-    }
-}
-
-bool icgn2d_variant_built(int variant) {
-    switch (variant) {
-#define X(ID, GG, MM, PP, WW, OO) \
-    case ID: return true;
-        OC_ICGN2D_VARIANTS(X)
-#undef X
-        case 8: return OC_BUILD_AB != 0;
-        case 9: return OC_BUILD_AB != 0;   // icgn2d_band.hip: measured 1.7 x slower, A/B build only
-        default: return false;
-    }
-}
-
 int icgn2d_setup_record_floats(int dof) { return sep::icgn2d_setup_floats(dof); }
-
-// largest sample count a variant can hold in LDS
-int icgn2d_max_samples(int variant) {
-    int g, mode, pipe, wpb, occ;
-    if (icgn2d_variant_info(variant, &g, &mode, &pipe, &wpb, &occ)) return 0;
-    if (variant == 9) return 0;  // (capi.hip asks icgn2d_band_supported instead)
-    const int arrays = mode == 0 ? 4 : ((mode == 4 || mode == 6 || mode == 2) ? 1 : 2);
-    // (half floats per sample slot, as in launch_t: the compact table of mode 6 takes 3 of them, the float table 6)
-    return kLdsBudget / ((2 * arrays * wpb + (mode == 6 ? 3 : mode >= 3 ? 6 : 0)) * ((int)sizeof(float) / 2) * kWave) * kWave;
-}
-
-bool icgn2d_compact_admissible(int variant, int rx, int ry, size_t count) { return count >= 32768 && icgn2d_compact_fits(variant, rx, ry); }
-
-bool icgn2d_compact_fits(int variant, int rx, int ry) {
-    if (variant != 10 && variant != 11) return false;
-    if (rx < 0 || ry < 0 || 2 * rx + 1 > 256 || 2 * ry + 1 > 256) return false;
-    const long long nt = ((2LL * rx + 1) * (2LL * ry + 1) + kWave - 1) / kWave;
-    // a workgroup: four target arrays of nt * 64 floats and the table's nt * 64 * 6 bytes (launch_t)
-    const long long lds = (4 * 4 + 6) * nt * kWave;
-    return (variant == 10 ? 6 : 4) * lds <= kLdsBudget;
-}
-
-int iclm2d_max_samples() { return kLdsBudget / (2 * (int)sizeof(float) * kWave) * kWave; }
 
 // p.arith_fma selects the build whose per-sample multiply-adds are fused (oc_device.h; icgn2d_fma.o)
 hipError_t launch_icgn2d1(const Icgn2dParams& p, float* pois, int stride_f, size_t count, int variant, bool xcd,

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "dic2d_device.h"
+#include "host/icgn2d_plan.h"  // the LDS budget and the one-pass table's footprint, which run_icgn2d's limit is computed from
 #include "oc_kernels.h"
 
 namespace ochip {
@@ -47,7 +48,7 @@ struct OnepassLaunch {
 };
 
 constexpr int kWpb = 8;                            // waves (POIs) per workgroup
-constexpr int kLdsBudget = 160 * 1024 - 2048;      // dynamic LDS; 2 KB stay free for the static area of the cooperative inverse
+constexpr int kLdsBudget = ochip_host::kIcgn2dLdsBudget;
 
 struct GradRef {
     float gx, gy, ref;
@@ -544,7 +545,7 @@ static hipError_t launch_dof(const Icgn2dParams& p, float* pois, int stride_f, s
     if (p.offsets || p.self_adaptive) return hipErrorNotSupported;  // one radius per launch, integer local coordinates
     const long long N = (2LL * p.rx + 1) * (2LL * p.ry + 1);
     const int nt = (int)((N + 63) / 64);
-    const size_t lds = (size_t)3 * nt * kWave * sizeof(float);
+    const size_t lds = ochip_host::icgn2d_onepass_lds_bytes((size_t)nt);
     if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
     auto kern = icgn2d_onepass_kernel<DOF>;
     // the dynamic-LDS limit is a per-device property of the loaded function: raised once on every device this process launches on
@@ -571,8 +572,6 @@ static hipError_t launch_dof(const Icgn2dParams& p, float* pois, int stride_f, s
 }
 
 }  // namespace onepass
-
-int icgn2d_onepass_max_samples() { return onepass::kLdsBudget / (3 * (int)sizeof(float) * kWave) * kWave; }
 
 hipError_t launch_icgn2d1_onepass(const Icgn2dParams& p, float* pois, int stride_f, size_t count, bool xcd, hipStream_t stream) {
     return onepass::launch_dof<6>(p, pois, stride_f, count, xcd, stream);

@@ -64,7 +64,6 @@ hipError_t launch_icgn2d1(const Icgn2dParams& p, float* pois, int stride_floats,
 // ICLM2D1 / ICLM2D2 (src/oc_iclm.cpp): the same kernel with the Levenberg-Marquardt step
 hipError_t launch_iclm2d1(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 hipError_t launch_iclm2d2(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
-int iclm2d_max_samples();
 hipError_t launch_icgn2d2(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, int variant, bool xcd,
                           hipStream_t stream, int phase = 0);
 int icgn2d_setup_record_floats(int dof);
@@ -101,24 +100,7 @@ hipError_t launch_icgn2d2_band(const Icgn2dParams& p, float* pois, int stride_fl
 // workgroup's coordinate table does not fit LDS.  p.arith_fma does not matter: the kernel is built with the fused multiply-add.
 hipError_t launch_icgn2d1_onepass(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 hipError_t launch_icgn2d2_onepass(const Icgn2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
-int icgn2d_onepass_max_samples();
-int icgn2d_variant_count();
-int icgn2d_variant_info(int variant, int* g, int* mode, int* pipe, int* wpb, int* occ);
-// variants 0 and 6 are A/B partners that only the A/B build of the library contains (-DOC_BUILD_AB=1)
-bool icgn2d_variant_built(int variant);
-// variants with a per-workgroup coordinate table (mode >= 3) need one subset radius per launch
-inline bool icgn2d_variant_uses_table(int variant) {
-    int g, mode, pipe, wpb, occ;
-    return icgn2d_variant_info(variant, &g, &mode, &pipe, &wpb, &occ) == 0 && mode >= 3;
-}
-// largest (2rx+1)*(2ry+1) a variant accepts
-int icgn2d_max_samples(int variant);
-// Variants 10 / 11 (4-wave workgroups on the compact coordinate table): whether a launch with ONE radius pair can run them -- at
-// most 256 columns and 256 rows (the table keeps them as bytes) and all six (variant 10) / four (variant 11) workgroups of a CU
-// inside its LDS -- and whether the automatic choice may take them: that, and count >= 32768 (a queue named through the
-// tuning key runs them at any length, as it runs variants 4 and 5).  Self-adaptive radii and IC-LM are the caller's to exclude.
-bool icgn2d_compact_fits(int variant, int rx, int ry);
-bool icgn2d_compact_admissible(int variant, int rx, int ry, size_t count);
+// (which variant ids exist, what each holds in LDS and which one a call launches: host/icgn2d_plan.h)
 
 // ---- poi_order.hip ---------------------------------------------------------
 // locality schedule: perm[k] = index of the k-th POI to visit (tile by tile, queue order inside a tile); tiles =
