@@ -15,6 +15,15 @@
  *     (src/oc_fftcc.cpp:145, src/oc_icgn.cpp:65, src/oc_image.cpp:43).
  *   - Per-POI failures stay in-band exactly like the reference: result.zncc is
  *     set to -3 / -4 / -5 (src/oc_dic.h:28-34) and nothing else is written.
+ *     One deviation: a POI whose own coordinate (x, y or z) is NaN is rejected
+ *     at the entry guard like a POI whose subset leaves the image -- -3 from
+ *     ICGN2D1/2D2, ICLM2D1/2D2 and ICGN3D1 (an incoming negative or NaN zncc is
+ *     kept), NR2D1's guard branch (-1, then its -4 / -5 rules), and FFTCC2D
+ *     leaves the record untouched.  The reference's guard is a chain of `<` and
+ *     `>` that a NaN passes, and it then indexes the images with (int)NaN, which
+ *     is undefined.  +-inf and out-of-image coordinates are rejected by the guard
+ *     as the reference writes it.  FFTCC3D has no guard in the reference and none
+ *     here: every index is clamped per element.
  *   - POIs are passed as the reference's own AoS records, updated in place:
  *     POI2D = 25 floats / 100 B (src/oc_poi.h:102-136), POI3D = 31 floats / 124 B
  *     (src/oc_poi.h:187-222).  `stride_bytes` lets a caller embed them in a

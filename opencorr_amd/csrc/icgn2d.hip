@@ -330,7 +330,9 @@ __global__ __launch_bounds__(64 * WPB, OCC) void icgn2d_kernel(Icgn2dParams P, f
 
     // guard, src/oc_icgn.cpp:160-167 (2D2: 705-712)
     // (the geometric part decides whether the POI has a set-up at all; the data part is what a later call may see differently)
-    const bool guard_geo = py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1;
+    // (written negated: a NaN coordinate fails every comparison, so it is rejected here like a subset that leaves the image,
+    // before any offset is formed from it -- the reference's form lets it through and then indexes with (int)NaN)
+    const bool guard_geo = !(py - ry >= 0 && px - rx >= 0 && py + ry <= height - 1 && px + rx <= width - 1);
     const bool guard_data = fabsf(u_in) >= width || fabsf(v_in) >= height || zncc_in < 0 || isnan(u_in) || isnan(v_in);
     if (guard_geo || (guard_data && !cache_fill)) {
         if (lane == 0) poi[poi2d::ZNCC] = zncc_in >= 0 ? -3.f : zncc_in;

@@ -141,7 +141,8 @@ __global__ __launch_bounds__(64 * kBandWaves, DOF == 6 ? 6 : 4) void icgn2d_band
         }
     }
     // guard, src/oc_icgn.cpp:160-167 (2D2: 705-712)
-    if (active && (py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1 || fabsf(u_in) >= width ||
+    // (the geometric part negated, as in icgn2d.hip: a NaN coordinate is rejected like a subset that leaves the image)
+    if (active && (!(py - ry >= 0 && px - rx >= 0 && py + ry <= height - 1 && px + rx <= width - 1) || fabsf(u_in) >= width ||
                    fabsf(v_in) >= height || zncc_in < 0 || isnan(u_in) || isnan(v_in))) {
         if (lane == 0) poi[poi2d::ZNCC] = zncc_in >= 0 ? -3.f : zncc_in;
         active = false;

@@ -288,8 +288,10 @@ __global__ __launch_bounds__(kBlock3d, 4) void icgn3d1_rows_kernel(Icgn3dParams 
         __syncthreads();  // everyone has read the record before anyone may overwrite it
 
         // guard, src/oc_icgn.cpp:1279-1286
-        if ((px - rx) < 0 || (py - ry) < 0 || (pz - rz) < 0 || (px + rx) > (DX - 1) || (py + ry) > (DY - 1) ||
-            (pz + rz) > (DZ - 1) || fabsf(init[0]) >= DX || fabsf(init[4]) >= DY || fabsf(init[8]) >= DZ ||
+        // (the geometric part written negated: a NaN coordinate fails every comparison, so it is rejected like a subvolume that
+        // leaves the image, before any address is formed from it)
+        if (!((px - rx) >= 0 && (py - ry) >= 0 && (pz - rz) >= 0 && (px + rx) <= (DX - 1) && (py + ry) <= (DY - 1) &&
+              (pz + rz) <= (DZ - 1)) || fabsf(init[0]) >= DX || fabsf(init[4]) >= DY || fabsf(init[8]) >= DZ ||
             zncc_in < 0 || isnan(init[0]) || isnan(init[4]) || isnan(init[8])) {
             if (tid == 0) poi[poi3d::ZNCC] = zncc_in >= 0 ? -3.f : zncc_in;
             continue;

@@ -93,7 +93,9 @@ __global__ __launch_bounds__(64 * kNrWaves, OC_NR_MINBLOCKS) void nr2d1_kernel(N
 
     // guard, src/oc_nr.cpp:165-171: a rejected POI gets -1 (not -3), and the two checks that follow
     // the else-branch (:304-316) still look at it, with the fields it came in with
-    if (py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1 || fabsf(u_in) >= width ||
+    // (the geometric part negated: a NaN coordinate fails every comparison and takes this branch, like a subset that leaves
+    // the image, before any offset is formed from it)
+    if (!(py - ry >= 0 && px - rx >= 0 && py + ry <= height - 1 && px + rx <= width - 1) || fabsf(u_in) >= width ||
         fabsf(v_in) >= height || zncc_in < 0 || isnan(u_in) || isnan(v_in)) {
         if (lane == 0) {
             float zncc = zncc_in < -1 ? zncc_in : -1.f;

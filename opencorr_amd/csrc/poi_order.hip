@@ -21,7 +21,9 @@ namespace {
 
 // 2D: `height` x `width` pixels, depth = 0; 3D (round 4, ICGN3D1): depth x height x width voxels, POI3D records (x, y, z first)
 __device__ __forceinline__ unsigned tile_of(const float* poi, int height, int width, int tile_px, int ntx, int depth = 0, int nty = 0) {
-    // NaN / out-of-image coordinates land in an edge tile; such POIs are rejected by the guards later anyway
+    // Only compares and clamps: an out-of-image coordinate lands in an edge tile, a NaN (every comparison false) in row / column 0.
+    // The solvers reject both at their guards -- the NaN because the guard's geometric part is written negated there
+    // (icgn2d.hip, icgn3d.hip); the reference's form of the guard would let it through.
     const float x = poi[poi2d::X], y = poi[poi2d::Y];
     const int xi = x >= 0.f ? (x < (float)width ? (int)x : width - 1) : 0;
     const int yi = y >= 0.f ? (y < (float)height ? (int)y : height - 1) : 0;

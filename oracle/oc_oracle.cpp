@@ -623,7 +623,9 @@ static void icgn2d_poi(const Images2D& im, int rx, int ry, float conv, float sto
 
     // guard, src/oc_icgn.cpp:160-167 (2D2: 705-712)
     const float u_in = p[0], v_in = p[6];
-    if (py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1 || std::fabs(u_in) >= width ||
+    // (the geometric part is written negated: a NaN coordinate fails every comparison and is rejected like a subset that
+    // leaves the image, as the GPU engine does; the reference's form lets it through and then indexes with (int)NaN)
+    if (!(py - ry >= 0 && px - rx >= 0 && py + ry <= height - 1 && px + rx <= width - 1) || std::fabs(u_in) >= width ||
         std::fabs(v_in) >= height || res[2] < 0 || std::isnan(u_in) || std::isnan(v_in)) {
         res[2] = res[2] >= 0 ? -3.f : res[2];
         return;
@@ -888,7 +890,8 @@ static void nr2d1_poi(const float* ref, const float* lut, const float* lut_gx, c
     float* res = poi + 14;  // u0 v0 zncc iteration convergence feature
     // guard, src/oc_nr.cpp:165-171: failure is -1 here (not -3), and the two checks after the
     // else-branch (:304-316) run for guarded POIs as well
-    if (py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1 || std::fabs(p[0]) >= width ||
+    // (the geometric part negated, so that a NaN coordinate takes this branch: see icgn2d_poi)
+    if (!(py - ry >= 0 && px - rx >= 0 && py + ry <= height - 1 && px + rx <= width - 1) || std::fabs(p[0]) >= width ||
         std::fabs(p[6]) >= height || res[2] < 0 || std::isnan(p[0]) || std::isnan(p[6])) {
         res[2] = res[2] < -1 ? res[2] : -1.f;
     } else {
@@ -1031,8 +1034,9 @@ static void icgn3d1_poi(const Images3D& im, int rx, int ry, int rz, float conv, 
     float* srad = poi + 28;  // subset_radius
     const int DX = im.dx, DY = im.dy, DZ = im.dz;
     // guard, src/oc_icgn.cpp:1279-1286
-    if ((px - rx) < 0 || (py - ry) < 0 || (pz - rz) < 0 || (px + rx) > (DX - 1) || (py + ry) > (DY - 1) ||
-        (pz + rz) > (DZ - 1) || std::fabs(p[0]) >= DX || std::fabs(p[4]) >= DY || std::fabs(p[8]) >= DZ || res[3] < 0 ||
+    // (the geometric part negated, so that a NaN coordinate is rejected: see icgn2d_poi)
+    if (!((px - rx) >= 0 && (py - ry) >= 0 && (pz - rz) >= 0 && (px + rx) <= (DX - 1) && (py + ry) <= (DY - 1) &&
+          (pz + rz) <= (DZ - 1)) || std::fabs(p[0]) >= DX || std::fabs(p[4]) >= DY || std::fabs(p[8]) >= DZ || res[3] < 0 ||
         std::isnan(p[0]) || std::isnan(p[4]) || std::isnan(p[8])) {
         res[3] = res[3] >= 0 ? -3.f : res[3];
         return;
@@ -1569,9 +1573,15 @@ void oc_oracle_fftcc2d(const float* ref, const float* tar, int height, int width
             float px = poi[0], py = poi[1];
             float gu = poi[2], gv = poi[8];  // deformation.u, deformation.v
             // src/oc_fftcc.cpp:190-196
-            if ((int)px < rx || (int)px >= width - rx || (int)py < ry || (int)py >= height - ry ||
-                (int)(px + gu) < rx || (int)(px + gu) >= width - rx || (int)(py + gv) < ry ||
-                (int)(py + gv) >= height - ry)
+            // A NaN, or a value no int holds, is rejected by name: the cast the reference relies on is undefined for
+            // it (the GPU's conversion gives 0 for NaN and saturates otherwise, and rejects every such value as well).
+            auto outside = [](float v, int lo, int hi) {
+                if (std::isnan(v) || std::fabs(v) >= 2147483648.f) return true;
+                const int i = (int)v;
+                return i < lo || i >= hi;
+            };
+            if (outside(px, rx, width - rx) || outside(py, ry, height - ry) || outside(px + gu, rx, width - rx) ||
+                outside(py + gv, ry, height - ry))
                 continue;
             float ref_mean = 0.f, tar_mean = 0.f, ref_norm = 0.f, tar_norm = 0.f;
             for (int r = 0; r < sh; r++)

@@ -211,7 +211,8 @@ void onepass_poi(const float* ref, const float* gxi, const float* gyi, const flo
     float* res = poi + 14;
     float* srad = poi + 23;
     const float u_in = p[0], v_in = p[6];
-    if (py - ry < 0 || px - rx < 0 || py + ry > height - 1 || px + rx > width - 1 || std::fabs(u_in) >= width ||
+    // (the geometric part negated, as the kernel has it: a NaN coordinate is rejected like a subset that leaves the image)
+    if (!(py - ry >= 0 && px - rx >= 0 && py + ry <= height - 1 && px + rx <= width - 1) || std::fabs(u_in) >= width ||
         std::fabs(v_in) >= height || res[2] < 0 || std::isnan(u_in) || std::isnan(v_in)) {
         res[2] = res[2] >= 0 ? -3.f : res[2];
         return;

@@ -199,7 +199,8 @@ void onepass_poi(const Images3D& im, int rx, int ry, int rz, float conv, float s
     float* res = poi + 15;   // u0 v0 w0 zncc iteration convergence
     float* srad = poi + 28;
     const int DX = im.dx, DY = im.dy, DZ = im.dz;
-    if ((px - rx) < 0 || (py - ry) < 0 || (pz - rz) < 0 || (px + rx) > (DX - 1) || (py + ry) > (DY - 1) || (pz + rz) > (DZ - 1) ||
+    // (the geometric part negated, as the kernel has it: a NaN coordinate is rejected like a subvolume that leaves the image)
+    if (!((px - rx) >= 0 && (py - ry) >= 0 && (pz - rz) >= 0 && (px + rx) <= (DX - 1) && (py + ry) <= (DY - 1) && (pz + rz) <= (DZ - 1)) ||
         std::fabs(p[0]) >= DX || std::fabs(p[4]) >= DY || std::fabs(p[8]) >= DZ || res[3] < 0 || std::isnan(p[0]) ||
         std::isnan(p[4]) || std::isnan(p[8])) {
         res[3] = res[3] >= 0 ? -3.f : res[3];

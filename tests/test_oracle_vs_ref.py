@@ -145,6 +145,26 @@ def test_self_adaptive_subsets_against_reference(pair, engine):
     _same(got, want)
 
 
+@pytest.mark.parametrize("offsets", [False, True])
+@pytest.mark.parametrize("engine", ["icgn2d1", "icgn2d2"])
+def test_non_finite_warp_terms_and_offsets_against_reference(engine, offsets):
+    """NaN and +-inf in the gradient terms of the guess and in the centre offsets (tests/nonfinite_cases.py, the WARP records, with the
+    clean ones): the reference is defined there -- the interpolation's range rule rejects the sample.  Records with a non-finite
+    COORDINATE never go to the compiled reference: it indexes with (int)NaN."""
+    import border_cases as bc
+    import nonfinite_cases as nf
+    case = nf.queue2d(offsets=offsets)
+    keep = (case.kind == nf.WARP) | case.clean
+    assert (case.kind[keep] == nf.WARP).sum() >= 30 and np.isfinite(case.queue[keep][:, :2]).all()
+    pois = case.queue[keep].copy()
+    kw = dict(center_offsets=case.offsets[keep].copy()) if offsets else {}
+    ref, tar = bc.pair2d(*nf.PAIR2D)
+    want, got = pois.copy(), pois.copy()
+    oref.solve2d(oref.ICGN2D1 if engine == "icgn2d1" else oref.ICGN2D2, ref, tar, bc.R2D[0], bc.R2D[1], bc.CONV, nf.STOP2D, want, **kw)
+    getattr(oracle, engine)(bc.prepared2d(*nf.PAIR2D), bc.R2D[0], bc.R2D[1], bc.CONV, nf.STOP2D, got, order=oracle.ORDER_SEQ, **kw)
+    _same(got, want)
+
+
 @pytest.mark.parametrize("dof,damping", [(6, (100.0, 0.1, 10.0)), (12, (100.0, 0.1, 10.0)), (6, (1.0, 0.5, 2.0))])
 def test_iclm2d_against_reference(pair, dof, damping):
     """ICLM2D1 / ICLM2D2 (src/oc_iclm.cpp).  The first damping value is powf(lambda, znssd / 4) - 1: glibc's powf here,
