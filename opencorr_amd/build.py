@@ -31,8 +31,9 @@ HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "dic2d_device.h", "
            # host logic without HIP calls; in a subfolder, so that kernel_fingerprint()'s listing of csrc/ (no PMC record goes stale
            # from a host-only change) does not see them
            os.path.join("host", "single_combiner.h"), os.path.join("host", "chunk_pipeline.h"),
-           # ... except this one, which KERNEL_SOURCES names: its variant list decides which ICGN2D kernels get instantiated
-           os.path.join("host", "icgn2d_plan.h")]
+           # ... except these two, which KERNEL_SOURCES names: the variant list of the first decides which ICGN2D kernels get
+           # instantiated, the lists of window sides of the second which FFTCC kernels
+           os.path.join("host", "icgn2d_plan.h"), os.path.join("host", "fftcc_plan.h")]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP vectoriser pairs independent scalar fp32 operations into v_pk_mul_f32 / v_pk_add_f32.  On gfx950 a
 # packed op occupies a SIMD for 4.3 cycles against 2.4 for the plain one (profiles/r02b_valu_ubench.json) -- a 10 % gain that the
@@ -53,13 +54,13 @@ FMA_SOURCES = ["icgn2d.hip", "icgn2d_band.hip", "icgn3d.hip"]
 KERNEL_SOURCES = {
     "icgn2d_kernel": ["icgn2d.hip", "dic2d_device.h", "oc_device.h", os.path.join("host", "icgn2d_plan.h")],
     "icgn2d_onepass_kernel": ["icgn2d_onepass.hip", "dic2d_device.h", "oc_device.h"],
-    "fftcc2d_fused32x2_kernel": ["fftcc2d_fused.hip", "fft_device.h", "oc_device.h"],
-    "fftcc2d_fusedn_kernel": ["fftcc2d_fusedn_impl.h", "fftcc2d_fusedn.hip", "fftcc2d_fusedp.hip", "fftcc2d_fusedr.hip", "fft_device.h", "oc_device.h"],
+    "fftcc2d_fused32x2_kernel": ["fftcc2d_fused.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
+    "fftcc2d_fusedn_kernel": ["fftcc2d_fusedn_impl.h", "fftcc2d_fusedn.hip", "fftcc2d_fusedp.hip", "fftcc2d_fusedr.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
     "icgn3d1": ["icgn3d.hip", "icgn3d_device.h", "oc_device.h"],
     "icgn3d_onepass_kernel": ["icgn3d_onepass.hip", "icgn3d_device.h", "oc_device.h"],
-    "fftcc3d_fused32_kernel": ["fftcc3d_fused.hip", "fft_device.h", "oc_device.h"],
+    "fftcc3d_fused32_kernel": ["fftcc3d_fused.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
     "match_top2_kernel": ["match.hip", "oc_device.h"],
-    "fftcc3d_planes_kernel": ["fftcc3d_planes_impl.h", "fftcc3d_planes.hip", "fftcc3d_planesb.hip", "fft_device.h", "oc_device.h"],
+    "fftcc3d_planes_kernel": ["fftcc3d_planes_impl.h", "fftcc3d_planes.hip", "fftcc3d_planesb.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
 }
 
 

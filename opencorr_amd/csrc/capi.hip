@@ -4,6 +4,7 @@
 // POI staging, rocFFT plans, stream and profiling events.  No CPU compute path
 // exists here: every compute call ends in HIP kernel launches or fails.
 #include "capi_internal.h"
+#include "host/fftcc_plan.h"
 #include "host/icgn2d_plan.h"
 
 namespace ochip_capi {
@@ -60,18 +61,6 @@ namespace {
 // ---------------------------------------------------------------------------
 // FFTCC2D pipeline
 // ---------------------------------------------------------------------------
-size_t fftcc_chunk_limit() {
-#if OC_BUILD_AB
-    // (experiments, A/B build only: POIs per batch of the rocFFT pipeline)
-    const char* s = getenv("OC_HIP_FFTCC_CHUNK");
-    if (s && *s) {
-        long v = atol(s);
-        if (v > 0) return (size_t)v;
-    }
-#endif
-    return 32768;
-}
-
 int ensure_fft(oc_hip_engine* e, size_t chunk) {
     // The reference plans fftwf_plan_dft_r2c_2d(width, height, ...) over a buffer filled
     // [r*width + c] (src/oc_fftcc.cpp:40-42, 204-221): n0 = 2rx is the slow dimension of
@@ -111,38 +100,20 @@ int ensure_fft(oc_hip_engine* e, size_t chunk) {
     return OC_HIP_OK;
 }
 
-int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
-    if (!e->img || e->img->ndim != 2) return fail(OC_HIP_ERR_INVALID, "FFTCC2D: set_images2d has not been called");
-    const ImagePair& im = *e->img;
-    // ("fftcc2d_fused" = 2: the generic NR x NC kernel also for 32 x 32 windows -- an A/B switch)
-    const bool fused32 = e->fftcc2d_fused != 2 && ochip::fftcc2d_fused_supported(e->rx, e->ry);
-    const bool rect = ochip::fftcc2d_rect_supported(e->rx, e->ry);   // rectangular windows without an instantiation (fftcc2d_rect.hip)
-    if (e->fftcc2d_fused && (fused32 || rect || ochip::fftcc2d_fusedn_supported(e->rx, e->ry))) {
-        ochip::Fftcc2dParams P = {im.ref_ptr(), im.tar_ptr(), im.dy, im.dx, e->rx, e->ry};
-        ProfScope prof(e);
-        const size_t kMaxBatch = 1u << 30;
-        for (size_t first = 0; first < count; first += kMaxBatch) {
-            const size_t n = (count - first) < kMaxBatch ? (count - first) : kMaxBatch;
-            float* q = d_pois + first * (size_t)stride_f;
-            hipError_t err = fused32 ? ochip::launch_fftcc2d_fused(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream, e->fftcc2d_fused)
-                             : rect  ? ochip::launch_fftcc2d_rect(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream)
-                                     : ochip::launch_fftcc2d_fusedn(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream);
-            if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "fused FFTCC2D launch failed: %s", hipGetErrorString(err));
-        }
-        return OC_HIP_OK;
-    }
-    const size_t chunk = count < fftcc_chunk_limit() ? count : fftcc_chunk_limit();
+// The rocFFT pipeline of FFTCC2D and FFTCC3D, what fftcc_plan.h calls RocFft: per batch of at most `chunk_limit` POIs gather ->
+// R2C over both windows -> conj(R) T -> C2R -> arg-max.  M floats per window, F complex bins per half spectrum; gather(pois, n,
+// ref_win, tar_win) and argmax(surfaces, pois, n) enqueue the engine's own kernels around the transforms.
+template <class Gather, class Argmax>
+int run_fftcc_rocfft(oc_hip_engine* e, float* d_pois, int stride_f, size_t count, size_t M, size_t F, size_t chunk_limit, Gather gather,
+                     Argmax argmax) {
+    const size_t chunk = count < chunk_limit ? count : chunk_limit;
     if (chunk == 0) return OC_HIP_OK;
     OC_TRY(ensure_fft(e, chunk));
-    const size_t M = (size_t)4 * e->rx * e->ry;                   // 2rx * 2ry
-    const size_t F = (size_t)(2 * e->rx) * (size_t)(e->ry + 1);   // n0 * (n1/2 + 1)
     OC_TRY(e->win.reserve(2 * chunk * M * sizeof(float)));
     OC_TRY(e->freq.reserve(2 * chunk * F * sizeof(float2)));
     OC_TRY(e->norms.reserve(2 * chunk * sizeof(float)));
-    OC_TRY(e->flags.reserve(chunk * sizeof(int)));
     OC_FFT_TRY(rocfft_execution_info_set_stream(e->fft.info_fwd, e->stream));
     OC_FFT_TRY(rocfft_execution_info_set_stream(e->fft.info_inv, e->stream));
-    ochip::Fftcc2dParams P = {im.ref_ptr(), im.tar_ptr(), im.dy, im.dx, e->rx, e->ry};
     float* ref_win = e->win.as<float>();
     float* tar_win = ref_win + chunk * M;
     float2* ref_freq = e->freq.as<float2>();
@@ -156,8 +127,7 @@ int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
             OC_HIP_TRY(hipMemsetAsync(ref_win + n * M, 0, (chunk - n) * M * sizeof(float), e->stream));
             OC_HIP_TRY(hipMemsetAsync(tar_win + n * M, 0, (chunk - n) * M * sizeof(float), e->stream));
         }
-        OC_HIP_TRY(ochip::launch_fftcc2d_gather(P, pois, stride_f, n, ref_win, tar_win, e->norms.as<float>(),
-                                                e->flags.as<int>(), e->stream));
+        OC_HIP_TRY(gather(pois, n, ref_win, tar_win));
         void* in_fwd[1] = {ref_win};
         void* out_fwd[1] = {ref_freq};
         OC_FFT_TRY(rocfft_execute(e->fft.fwd, in_fwd, out_fwd, e->fft.info_fwd));
@@ -165,8 +135,44 @@ int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
         void* in_inv[1] = {ref_freq};
         void* out_inv[1] = {ref_win};  // correlation surfaces overwrite the reference windows
         OC_FFT_TRY(rocfft_execute(e->fft.inv, in_inv, out_inv, e->fft.info_inv));
-        OC_HIP_TRY(ochip::launch_fftcc2d_argmax(P, ref_win, e->norms.as<float>(), e->flags.as<int>(), pois, stride_f,
-                                                n, e->stream));
+        OC_HIP_TRY(argmax(ref_win, pois, n));
+    }
+    return OC_HIP_OK;
+}
+
+int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
+    using ochip_host::Fftcc2dKernel;
+    if (!e->img || e->img->ndim != 2) return fail(OC_HIP_ERR_INVALID, "FFTCC2D: set_images2d has not been called");
+    const ImagePair& im = *e->img;
+    const ochip::Fftcc2dParams P = {im.ref_ptr(), im.tar_ptr(), im.dy, im.dx, e->rx, e->ry};
+    const Fftcc2dKernel kernel = ochip_host::fftcc2d_kernel(e->rx, e->ry, e->fftcc2d_fused);
+    if (kernel == Fftcc2dKernel::RocFft) {
+        const size_t chunk = ochip_host::kFftcc2dRocfftChunk;
+        OC_TRY(e->flags.reserve((count < chunk ? count : chunk) * sizeof(int)));   // the bounds guard's verdicts, gather -> arg-max
+        return run_fftcc_rocfft(
+            e, d_pois, stride_f, count, ochip_host::fftcc_rocfft_window_floats(e->rx, e->ry, 0), ochip_host::fftcc_rocfft_bins(e->rx, e->ry, 0), chunk,
+            [&](const float* pois, size_t n, float* ref_win, float* tar_win) {
+                return ochip::launch_fftcc2d_gather(P, pois, stride_f, n, ref_win, tar_win, e->norms.as<float>(), e->flags.as<int>(), e->stream);
+            },
+            [&](const float* surf, float* pois, size_t n) {
+                return ochip::launch_fftcc2d_argmax(P, surf, e->norms.as<float>(), e->flags.as<int>(), pois, stride_f, n, e->stream);
+            });
+    }
+    const bool xcd = e->icgn2d_xcd != 0;
+    ProfScope prof(e);
+    for (size_t first = 0; first < count; first += ochip_host::kFftccMaxLaunch) {
+        const size_t n = (count - first) < ochip_host::kFftccMaxLaunch ? (count - first) : ochip_host::kFftccMaxLaunch;
+        float* q = d_pois + first * (size_t)stride_f;
+        hipError_t err = hipErrorInvalidValue;
+        switch (kernel) {
+            case Fftcc2dKernel::Fused32: err = ochip::launch_fftcc2d_fused(P, q, stride_f, n, xcd, e->stream, e->fftcc2d_fused); break;
+            case Fftcc2dKernel::Smooth: err = ochip::launch_fftcc2d_fusedn(P, q, stride_f, n, xcd, e->stream); break;
+            case Fftcc2dKernel::Prime: err = ochip::launch_fftcc2d_fusedp(P, q, stride_f, n, xcd, e->stream); break;
+            case Fftcc2dKernel::Pair: err = ochip::launch_fftcc2d_fusedr(P, q, stride_f, n, xcd, e->stream); break;
+            case Fftcc2dKernel::Rect: err = ochip::launch_fftcc2d_rect(P, q, stride_f, n, xcd, e->stream); break;
+            case Fftcc2dKernel::RocFft: break;   // (served above)
+        }
+        if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "fused FFTCC2D launch failed: %s", hipGetErrorString(err));
     }
     return OC_HIP_OK;
 }
@@ -416,17 +422,6 @@ int run_nr2d1(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
 // ---------------------------------------------------------------------------
 // FFTCC3D pipeline / ICGN3D1
 // ---------------------------------------------------------------------------
-size_t fftcc3d_chunk_limit() {
-#if OC_BUILD_AB
-    const char* s = getenv("OC_HIP_FFTCC3D_CHUNK");
-    if (s && *s) {
-        long v = atol(s);
-        if (v > 0) return (size_t)v;
-    }
-#endif
-    return 1024;
-}
-
 // visiting order of a POI3D queue in compact cubic blocks (poi_order.hip): FFTCC3D's single-kernel paths and ICGN3D1
 int tile_order3d(oc_hip_engine* e, const float* d_pois, int stride_f, size_t count, int tile_vox, const unsigned** perm) {
     *perm = nullptr;
@@ -442,78 +437,51 @@ int tile_order3d(oc_hip_engine* e, const float* d_pois, int stride_f, size_t cou
 }
 
 int run_fftcc3d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
+    using ochip_host::Fftcc3dKernel;
     if (!e->img || e->img->ndim != 3) return fail(OC_HIP_ERR_INVALID, "FFTCC3D: set_images3d has not been called");
     const ImagePair& im = *e->img;
-    const bool fused32 = ochip::fftcc3d_fused_supported(e->rx, e->ry, e->rz);
-    if (e->fftcc3d_fused && ochip::fftcc3d_planes_supported(e->rx, e->ry, e->rz)) {
+    ochip::Fftcc3dParams P = {im.ref_ptr(), im.tar_ptr(), im.dz, im.dy, im.dx, e->rx, e->ry, e->rz};
+    const Fftcc3dKernel kernel = ochip_host::fftcc3d_kernel(e->rx, e->ry, e->rz, e->fftcc3d_fused, OC_BUILD_AB != 0);
+    if (kernel == Fftcc3dKernel::RocFft)
+        return run_fftcc_rocfft(
+            e, d_pois, stride_f, count, ochip_host::fftcc_rocfft_window_floats(e->rx, e->ry, e->rz), ochip_host::fftcc_rocfft_bins(e->rx, e->ry, e->rz),
+            ochip_host::kFftcc3dRocfftChunk,
+            [&](const float* pois, size_t n, float* ref_win, float* tar_win) {
+                return ochip::launch_fftcc3d_gather(P, pois, stride_f, n, ref_win, tar_win, e->norms.as<float>(), e->stream);
+            },
+            [&](const float* surf, float* pois, size_t n) { return ochip::launch_fftcc3d_argmax(P, surf, e->norms.as<float>(), pois, stride_f, n, e->stream); });
+    if (kernel == Fftcc3dKernel::Planes) {
         // cubes too large for the chip: persistent workgroups, each with a private complex N^3 scratch volume (fftcc3d_planes.hip)
-        ochip::Fftcc3dParams P = {im.ref_ptr(), im.tar_ptr(), im.dz, im.dy, im.dx, e->rx, e->ry, e->rz};
-        int blocks = e->fftcc3d_planes_blocks > 0 ? e->fftcc3d_planes_blocks : 256;
-        blocks = (blocks + 7) / 8 * 8;
-        if ((size_t)blocks > (count + 7) / 8 * 8) blocks = (int)((count + 7) / 8 * 8);
-        OC_TRY(e->win.reserve(ochip::fftcc3d_planes_scratch_bytes(e->rx, blocks)));
+        const int blocks = ochip_host::fftcc3d_planes_blocks(e->fftcc3d_planes_blocks, count);
+        OC_TRY(e->win.reserve(ochip_host::fftcc3d_planes_scratch_bytes(e->rx, blocks)));
         OC_TRY(tile_order3d(e, d_pois, stride_f, count, e->fftcc3d_tile_vox, &P.perm));
         ProfScope prof(e);
         hipError_t err = ochip::launch_fftcc3d_planes(P, d_pois, stride_f, count, e->win.p, blocks, e->stream);
         if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "plane-wise FFTCC3D kernel launch failed: %s", hipGetErrorString(err));
         return OC_HIP_OK;
     }
-    const bool box = ochip::fftcc3d_box_supported(e->rx, e->ry, e->rz);   // non-cubic windows (fftcc3d_box.hip)
-    if (e->fftcc3d_fused && (fused32 || box || ochip::fftcc3d_fusedn_supported(e->rx, e->ry, e->rz))) {
-        ochip::Fftcc3dParams P = {im.ref_ptr(), im.tar_ptr(), im.dz, im.dy, im.dx, e->rx, e->ry, e->rz};
-        if (count <= (1u << 30)) OC_TRY(tile_order3d(e, d_pois, stride_f, count, e->fftcc3d_tile_vox, &P.perm));
-        ProfScope prof(e);
-        const size_t kMaxGrid = 1u << 30;
-#if OC_BUILD_AB
-        const bool fused32_r5 = fused32 && e->fftcc3d_fused == 2;   // the decomposition of rounds 1 - 5 (fftcc3d_fused_r5.hip)
-        if (fused32_r5) OC_TRY(e->flags.reserve(ochip::fftcc3d_fused_flag_bytes(count < kMaxGrid ? count : kMaxGrid)));   // once, before anything is enqueued
-#endif
-        for (size_t first = 0; first < count; first += kMaxGrid) {
-            const size_t n = (count - first) < kMaxGrid ? (count - first) : kMaxGrid;
-            float* q = d_pois + first * (size_t)stride_f;
-            hipError_t err =
-#if OC_BUILD_AB
-                             fused32_r5 ? ochip::launch_fftcc3d_fused_r5(P, q, stride_f, n, e->icgn2d_xcd != 0, e->flags.as<unsigned char>(), e->stream) :
-#endif
-                             fused32 ? ochip::launch_fftcc3d_fused(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream)
-                             : box   ? ochip::launch_fftcc3d_box(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream)
-                                     : ochip::launch_fftcc3d_fusedn(P, q, stride_f, n, e->icgn2d_xcd != 0, e->stream);
-            if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "fused FFTCC3D kernel launch failed: %s", hipGetErrorString(err));
-        }
-        return OC_HIP_OK;
-    }
-    const size_t chunk = count < fftcc3d_chunk_limit() ? count : fftcc3d_chunk_limit();
-    if (chunk == 0) return OC_HIP_OK;
-    OC_TRY(ensure_fft(e, chunk));
-    const size_t M = (size_t)8 * e->rx * e->ry * e->rz;
-    const size_t F = (size_t)(2 * e->rx) * (size_t)(2 * e->ry) * (size_t)(e->rz + 1);
-    OC_TRY(e->win.reserve(2 * chunk * M * sizeof(float)));
-    OC_TRY(e->freq.reserve(2 * chunk * F * sizeof(float2)));
-    OC_TRY(e->norms.reserve(2 * chunk * sizeof(float)));
-    OC_FFT_TRY(rocfft_execution_info_set_stream(e->fft.info_fwd, e->stream));
-    OC_FFT_TRY(rocfft_execution_info_set_stream(e->fft.info_inv, e->stream));
-    ochip::Fftcc3dParams P = {im.ref_ptr(), im.tar_ptr(), im.dz, im.dy, im.dx, e->rx, e->ry, e->rz};
-    float* ref_win = e->win.as<float>();
-    float* tar_win = ref_win + chunk * M;
-    float2* ref_freq = e->freq.as<float2>();
-    float2* tar_freq = ref_freq + chunk * F;
+    const size_t kMaxGrid = ochip_host::kFftccMaxLaunch;
+    if (count <= kMaxGrid) OC_TRY(tile_order3d(e, d_pois, stride_f, count, e->fftcc3d_tile_vox, &P.perm));
+    const bool xcd = e->icgn2d_xcd != 0;
     ProfScope prof(e);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t n = (count - first) < chunk ? (count - first) : chunk;
-        float* pois = d_pois + first * (size_t)stride_f;
-        if (n < chunk) {
-            OC_HIP_TRY(hipMemsetAsync(ref_win + n * M, 0, (chunk - n) * M * sizeof(float), e->stream));
-            OC_HIP_TRY(hipMemsetAsync(tar_win + n * M, 0, (chunk - n) * M * sizeof(float), e->stream));
+#if OC_BUILD_AB
+    // the decomposition of rounds 1 - 5 (fftcc3d_fused_r5.hip): its flags once, before anything is enqueued
+    if (kernel == Fftcc3dKernel::Fused32R5) OC_TRY(e->flags.reserve(ochip::fftcc3d_fused_flag_bytes(count < kMaxGrid ? count : kMaxGrid)));
+#endif
+    for (size_t first = 0; first < count; first += kMaxGrid) {
+        const size_t n = (count - first) < kMaxGrid ? (count - first) : kMaxGrid;
+        float* q = d_pois + first * (size_t)stride_f;
+        hipError_t err = hipErrorInvalidValue;
+        switch (kernel) {
+            case Fftcc3dKernel::Fused32: err = ochip::launch_fftcc3d_fused(P, q, stride_f, n, xcd, e->stream); break;
+#if OC_BUILD_AB
+            case Fftcc3dKernel::Fused32R5: err = ochip::launch_fftcc3d_fused_r5(P, q, stride_f, n, xcd, e->flags.as<unsigned char>(), e->stream); break;
+#endif
+            case Fftcc3dKernel::Cube: err = ochip::launch_fftcc3d_fusedn(P, q, stride_f, n, xcd, e->stream); break;
+            case Fftcc3dKernel::Box: err = ochip::launch_fftcc3d_box(P, q, stride_f, n, xcd, e->stream); break;
+            default: break;   // (RocFft and Planes are served above; no Fused32R5 outside the A/B build)
         }
-        OC_HIP_TRY(ochip::launch_fftcc3d_gather(P, pois, stride_f, n, ref_win, tar_win, e->norms.as<float>(), e->stream));
-        void* in_fwd[1] = {ref_win};
-        void* out_fwd[1] = {ref_freq};
-        OC_FFT_TRY(rocfft_execute(e->fft.fwd, in_fwd, out_fwd, e->fft.info_fwd));
-        OC_HIP_TRY(ochip::launch_fftcc_conjmul(ref_freq, tar_freq, ref_freq, n * F, e->stream));
-        void* in_inv[1] = {ref_freq};
-        void* out_inv[1] = {ref_win};
-        OC_FFT_TRY(rocfft_execute(e->fft.inv, in_inv, out_inv, e->fft.info_inv));
-        OC_HIP_TRY(ochip::launch_fftcc3d_argmax(P, ref_win, e->norms.as<float>(), pois, stride_f, n, e->stream));
+        if (err != hipSuccess) return fail(OC_HIP_ERR_HIP, "fused FFTCC3D kernel launch failed: %s", hipGetErrorString(err));
     }
     return OC_HIP_OK;
 }

@@ -22,6 +22,7 @@
 #include "dic2d_device.h"
 #include "fft_device.h"
 #include "oc_kernels.h"
+#include "host/fftcc_plan.h"
 
 namespace ochip {
 
@@ -29,7 +30,7 @@ namespace {
 
 using namespace fftdev;
 
-constexpr int FN = 32;               // window side (2 * radius)
+constexpr int FN = ochip_host::kFftcc2dFusedSide;   // window side (2 * radius): 32
 constexpr int FP = FN + 1;           // LDS row pitch in complex elements
 constexpr int FWAVE_LDS = FN * FP;   // float2 elements per wave
 // OC_FFTCC2D_X2 = 1 (the default since round 3) launches the two-POIs-per-wave kernel further down instead of this one.
@@ -447,12 +448,10 @@ __global__ __launch_bounds__(64 * kX2Waves, OC_FFTCC2D_X2_OCC) void fftcc2d_fuse
     }
 }
 
-bool fftcc2d_fused_supported(int rx, int ry) { return rx == FN / 2 && ry == FN / 2; }
-
 hipError_t launch_fftcc2d_fused(const Fftcc2dParams& p, float* pois, int stride_f, size_t count, bool xcd,
                                 hipStream_t stream, int body) {
     if (count == 0) return hipSuccess;
-    if (!fftcc2d_fused_supported(p.rx, p.ry)) return hipErrorInvalidValue;
+    if (ochip_host::fftcc2d_kernel(p.rx, p.ry, 1) != ochip_host::Fftcc2dKernel::Fused32) return hipErrorInvalidValue;
     (void)hipGetLastError();  // drop stale errors of earlier, unrelated calls
 #if OC_FFTCC2D_X2
     {

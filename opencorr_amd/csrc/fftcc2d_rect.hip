@@ -1,5 +1,6 @@
 // fftcc2d_rect.hip -- FFTCC2D in ONE kernel for the RECTANGULAR windows (rx != ry, both radii 4 ... 32) that have no
-// instantiation of the register-FFT template: everything outside the 42 pairs of fftcc2d_fusedr.hip.
+// instantiation of the register-FFT template: everything outside the 42 pairs of fftcc2d_fusedr.hip (host/fftcc_plan.h:
+// Fftcc2dKernel::Rect, and fftcc2d_rect_maxn for the instantiation).
 //
 // FFTCC2D's constructor takes two radii (src/oc_fftcc.cpp:36-43 plans any 2rx x 2ry window); 29 x 28 side pairs are too many
 // instantiations of fftcc2d_fusedn_impl.h, so -- like fftcc3d_box.hip in 3D -- this kernel takes the two sides at run time and
@@ -18,10 +19,9 @@
 #include "oc_device.h"
 #include "fft_device.h"
 #include "oc_kernels.h"
+#include "host/fftcc_plan.h"
 
 namespace ochip {
-
-bool fftcc2d_fusedr_supported(int rx, int ry);  // fftcc2d_fusedr.hip: the 42 pairs with a kernel of their own
 
 namespace {
 
@@ -231,17 +231,14 @@ hipError_t launch_rect(const Fftcc2dParams& p, float* pois, int stride_f, size_t
 
 }  // namespace
 
-// rectangular windows with both radii in 4 ... 32 that fftcc2d_fusedr.hip has no instantiation for
-bool fftcc2d_rect_supported(int rx, int ry) {
-    return rx != ry && rx >= 4 && rx <= 32 && ry >= 4 && ry <= 32 && !fftcc2d_fusedr_supported(rx, ry);
-}
-
 hipError_t launch_fftcc2d_rect(const Fftcc2dParams& p, float* pois, int stride_f, size_t count, bool xcd, hipStream_t stream) {
     if (count == 0) return hipSuccess;
-    if (!fftcc2d_rect_supported(p.rx, p.ry)) return hipErrorInvalidValue;
-    if (p.rx <= 16 && p.ry <= 16) return launch_rect<32>(p, pois, stride_f, count, xcd, stream);
-    if (p.rx <= 24 && p.ry <= 24) return launch_rect<48>(p, pois, stride_f, count, xcd, stream);
-    return launch_rect<64>(p, pois, stride_f, count, xcd, stream);
+    if (ochip_host::fftcc2d_kernel(p.rx, p.ry, 1) != ochip_host::Fftcc2dKernel::Rect) return hipErrorInvalidValue;
+    switch (ochip_host::fftcc2d_rect_maxn(p.rx, p.ry)) {
+        case 32: return launch_rect<32>(p, pois, stride_f, count, xcd, stream);
+        case 48: return launch_rect<48>(p, pois, stride_f, count, xcd, stream);
+        default: return launch_rect<64>(p, pois, stride_f, count, xcd, stream);
+    }
 }
 
 }  // namespace ochip

@@ -27,6 +27,7 @@
 #include "oc_device.h"
 #include "fft_device.h"
 #include "oc_kernels.h"
+#include "host/fftcc_plan.h"
 
 #include <atomic>
 
@@ -36,10 +37,11 @@ namespace {
 
 using namespace fftdev;
 
-constexpr int kBoxMaxSide = 32;
+constexpr int kBoxMaxSide = ochip_host::kFftcc3dBoxMaxSide;   // 32
 constexpr int kBoxMaxThreads = kBoxMaxSide * kBoxMaxSide;
-constexpr int kBoxMaxWaves = kBoxMaxThreads / kWave;
-constexpr size_t kBoxLdsLimit = 160 * 1024;
+constexpr int kBoxMaxWaves = ochip_host::kFftcc3dBoxMaxWaves;
+constexpr size_t kBoxLdsLimit = ochip_host::kFftcc3dBoxLdsLimit;
+static_assert(kBoxMaxWaves * kWave == kBoxMaxThreads && sizeof(c2) == 2 * sizeof(float), "fftcc3d_box_lds_bytes (host/fftcc_plan.h) counts these");
 
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));  // 4-byte aligned 16-byte load
 
@@ -285,31 +287,17 @@ __global__ __launch_bounds__(kBoxMaxThreads) void fftcc3d_box_kernel(Fftcc3dPara
     }
 }
 
-size_t box_lds_bytes(int rx, int ry, int rz) {
-    const size_t nx = 2 * (size_t)rx, ny = 2 * (size_t)ry, nz = 2 * (size_t)rz;
-    return nx * ny * (nz + 1) * sizeof(c2) +   // [n0 = 2rx][n1 = 2ry][2rz + 1]
-           6 * kBoxMaxSide * sizeof(int) + 2 * kBoxMaxWaves * sizeof(float) + kBoxMaxWaves * sizeof(int);
-}
-
 }  // namespace
-
-// non-cubic windows with every radius in 4 ... 16 whose complex volume fits the LDS (the cubes have kernels of their own)
-bool fftcc3d_box_supported(int rx, int ry, int rz) {
-    const auto ok = [](int r) { return r >= 4 && r <= kBoxMaxSide / 2; };
-    if (!ok(rx) || !ok(ry) || !ok(rz)) return false;
-    if (rx == ry && ry == rz) return false;
-    return box_lds_bytes(rx, ry, rz) <= kBoxLdsLimit;
-}
 
 hipError_t launch_fftcc3d_box(const Fftcc3dParams& p, float* pois, int stride_f, size_t count, bool xcd, hipStream_t stream) {
     if (count == 0) return hipSuccess;
-    if (!fftcc3d_box_supported(p.rx, p.ry, p.rz)) return hipErrorInvalidValue;
+    if (ochip_host::fftcc3d_kernel(p.rx, p.ry, p.rz, 1, false) != ochip_host::Fftcc3dKernel::Box) return hipErrorInvalidValue;
     const int nx = 2 * p.rx, ny = 2 * p.ry, nz = 2 * p.rz;
     int lines = nz * ny;   // (lines per pass: the products of two sides, whichever axis is the fast one)
     if (nz * nx > lines) lines = nz * nx;
     if (ny * nx > lines) lines = ny * nx;
     const int block = (lines + kWave - 1) / kWave * kWave;
-    const size_t lds = box_lds_bytes(p.rx, p.ry, p.rz);
+    const size_t lds = ochip_host::fftcc3d_box_lds_bytes(p.rx, p.ry, p.rz);
     // more than 64 KB of dynamic LDS has to be asked for, once per device (benign race: every caller sets the same value)
     static std::atomic<unsigned long long> attr_set{0};
     int dev = 0;

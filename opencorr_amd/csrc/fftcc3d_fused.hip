@@ -47,6 +47,7 @@
 #include "oc_device.h"
 #include "fft_device.h"
 #include "oc_kernels.h"
+#include "host/fftcc_plan.h"
 
 #if defined(OC_F32_TIMELINE) && !OC_BUILD_AB
 #error "OC_F32_TIMELINE is a timing experiment of the A/B builds (tools/ab_build.py ... -DOC_BUILD_AB=1)"
@@ -58,7 +59,7 @@ namespace {
 
 using namespace fftdev;
 
-constexpr int TN = 32;                     // window side (2 * radius)
+constexpr int TN = ochip_host::kFftcc3dFusedSide;   // window side (2 * radius): 32
 constexpr int TP = TN + 1;                 // row pitch (floats) of the plane slots of the y -> x exchange
 constexpr int kThreads3 = TN * TN;         // one line per thread
 constexpr int kWaves = kThreads3 / kWave;  // 16
@@ -366,11 +367,9 @@ __global__ __launch_bounds__(kThreads3, 4) void fftcc3d_fused32_kernel(Fftcc3dPa
 
 }  // namespace
 
-bool fftcc3d_fused_supported(int rx, int ry, int rz) { return rx == TN / 2 && ry == TN / 2 && rz == TN / 2; }
-
 hipError_t launch_fftcc3d_fused(const Fftcc3dParams& p, float* pois, int stride_f, size_t count, bool xcd, hipStream_t stream) {
     if (count == 0) return hipSuccess;
-    if (!fftcc3d_fused_supported(p.rx, p.ry, p.rz)) return hipErrorInvalidValue;
+    if (ochip_host::fftcc3d_kernel(p.rx, p.ry, p.rz, 1, false) != ochip_host::Fftcc3dKernel::Fused32) return hipErrorInvalidValue;
     const int chunk = xcd ? (int)((count + 7) / 8) : 0;
     const size_t grid = xcd ? (size_t)chunk * 8 : count;
     (void)hipGetLastError();  // drop stale errors of earlier, unrelated calls

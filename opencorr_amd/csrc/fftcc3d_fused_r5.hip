@@ -25,6 +25,7 @@
 #include "oc_device.h"
 #include "fft_device.h"
 #include "oc_kernels.h"
+#include "host/fftcc_plan.h"
 
 // OC_FUSED32_WAVE_XY: 1 = the x <-> y exchanges synchronise inside the half-wave that owns a z-plane (a wave-level fence) and
 // keep only the workgroup barrier between the two z-halves; 0 = two workgroup barriers per half (rounds 1 - 3).  Config E:
@@ -399,7 +400,7 @@ size_t fftcc3d_fused_flag_bytes(size_t count) { return ((count + 3) & ~(size_t)3
 hipError_t launch_fftcc3d_fused_r5(const Fftcc3dParams& p, float* pois, int stride_f, size_t count, bool xcd, unsigned char* needs_clamped,
                                 hipStream_t stream) {
     if (count == 0) return hipSuccess;
-    if (!fftcc3d_fused_supported(p.rx, p.ry, p.rz) || !needs_clamped) return hipErrorInvalidValue;
+    if (ochip_host::fftcc3d_kernel(p.rx, p.ry, p.rz, 2, true) != ochip_host::Fftcc3dKernel::Fused32R5 || !needs_clamped) return hipErrorInvalidValue;
     const int chunk = xcd ? (int)((count + 7) / 8) : 0;
     const size_t grid = xcd ? (size_t)chunk * 8 : count;
     (void)hipGetLastError();  // drop stale errors of earlier, unrelated calls

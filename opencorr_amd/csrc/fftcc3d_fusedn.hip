@@ -19,6 +19,7 @@
 #include "oc_device.h"
 #include "fft_device.h"
 #include "oc_kernels.h"
+#include "host/fftcc_plan.h"
 
 namespace ochip {
 
@@ -295,23 +296,14 @@ hipError_t launch_cube(const Fftcc3dParams& p, float* pois, int stride_f, size_t
 
 }  // namespace
 
-// cubic windows of side 8 ... 26 (radius 4 ... 13)
-bool fftcc3d_fusedn_supported(int rx, int ry, int rz) { return rx == ry && ry == rz && rx >= 4 && rx <= 13; }
-
 hipError_t launch_fftcc3d_fusedn(const Fftcc3dParams& p, float* pois, int stride_f, size_t count, bool xcd, hipStream_t stream) {
     if (count == 0) return hipSuccess;
-    if (!fftcc3d_fusedn_supported(p.rx, p.ry, p.rz)) return hipErrorInvalidValue;
+    if (ochip_host::fftcc3d_kernel(p.rx, p.ry, p.rz, 1, false) != ochip_host::Fftcc3dKernel::Cube) return hipErrorInvalidValue;
     switch (2 * p.rx) {
-        case 8: return launch_cube<8>(p, pois, stride_f, count, xcd, stream);
-        case 10: return launch_cube<10>(p, pois, stride_f, count, xcd, stream);
-        case 12: return launch_cube<12>(p, pois, stride_f, count, xcd, stream);
-        case 14: return launch_cube<14>(p, pois, stride_f, count, xcd, stream);
-        case 16: return launch_cube<16>(p, pois, stride_f, count, xcd, stream);
-        case 18: return launch_cube<18>(p, pois, stride_f, count, xcd, stream);
-        case 20: return launch_cube<20>(p, pois, stride_f, count, xcd, stream);
-        case 22: return launch_cube<22>(p, pois, stride_f, count, xcd, stream);
-        case 24: return launch_cube<24>(p, pois, stride_f, count, xcd, stream);
-        case 26: return launch_cube<26>(p, pois, stride_f, count, xcd, stream);
+#define OC_CUBE_CASE(NN) \
+    case NN: return launch_cube<NN>(p, pois, stride_f, count, xcd, stream);
+        OC_FFTCC3D_CUBE_SIDES(OC_CUBE_CASE)
+#undef OC_CUBE_CASE
         default: return hipErrorInvalidValue;
     }
 }

@@ -263,22 +263,26 @@ hipError_t launch_fftcc_conjmul(const float2* rf, const float2* tf, float2* zf, 
 hipError_t launch_fftcc2d_argmax(const Fftcc2dParams& p, const float* surf, const float* norms, const int* flags,
                                  float* pois, int stride_floats, size_t count, hipStream_t stream);
 
-// ---- fftcc2d_fusedn.hip ----------------------------------------------------
-// the same for square windows of side 20, 24, 30, 36, 40, 48 (radii 10, 12, 15, 18, 20, 24): mixed-radix FFT, one line
-// per lane
-bool fftcc2d_fusedn_supported(int rx, int ry);
+// The single-kernel paths of FFTCC2D: the whole FFTCC2D::compute on chip, no rocFFT, no scratch.  Which window each of them
+// serves -- the lists of instantiated sides and the rule -- is host/fftcc_plan.h (fftcc2d_kernel); every launcher refuses a
+// window the plan gives to another one with hipErrorInvalidValue.
+// ---- fftcc2d_fusedn.hip / fftcc2d_fusedp.hip / fftcc2d_fusedr.hip -------------
+// one template (fftcc2d_fusedn_impl.h), one line per lane: square windows with 5-smooth sides (Fftcc2dKernel::Smooth), square
+// windows whose side has a prime factor of 7 ... 31 (Prime), rectangular windows with both sides out of a short list (Pair)
 hipError_t launch_fftcc2d_fusedn(const Fftcc2dParams& p, float* pois, int stride_floats, size_t count, bool xcd,
+                                 hipStream_t stream);
+hipError_t launch_fftcc2d_fusedp(const Fftcc2dParams& p, float* pois, int stride_floats, size_t count, bool xcd,
+                                 hipStream_t stream);
+hipError_t launch_fftcc2d_fusedr(const Fftcc2dParams& p, float* pois, int stride_floats, size_t count, bool xcd,
                                  hipStream_t stream);
 
 // ---- fftcc2d_rect.hip ------------------------------------------------------
-// the same for every OTHER rectangular window with both radii in 4 ... 32: ONE kernel (two instantiations: sides <= 32, sides
-// <= 64), the two sides are run-time values (each axis pass switches to the line transform of its length)
-bool fftcc2d_rect_supported(int rx, int ry);
+// every OTHER rectangular window inside the plan's radius range (Rect): ONE kernel in three instantiations (fftcc2d_rect_maxn),
+// the two sides are run-time values (each axis pass switches to the line transform of its length)
 hipError_t launch_fftcc2d_rect(const Fftcc2dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 
 // ---- fftcc2d_fused.hip -----------------------------------------------------
-// whole FFTCC2D::compute for 32 x 32 windows (rx == ry == 16) in one kernel, no rocFFT, no scratch
-bool fftcc2d_fused_supported(int rx, int ry);
+// 32 x 32 windows (Fused32)
 // body: 3 / 4 / 5 = the A/B partners of the gfx950 instruction-count work (fftcc2d_fused.hip), anything else = the default
 hipError_t launch_fftcc2d_fused(const Fftcc2dParams& p, float* pois, int stride_floats, size_t count, bool xcd,
                                 hipStream_t stream, int body = 1);
@@ -299,12 +303,13 @@ hipError_t launch_fftcc3d_gather(const Fftcc3dParams& p, const float* pois, int 
 hipError_t launch_fftcc3d_argmax(const Fftcc3dParams& p, const float* surf, const float* norms, float* pois,
                                  int stride_floats, size_t count, hipStream_t stream);
 
+// The single-kernel paths of FFTCC3D, all of FFTCC3D::compute(POI3D*) in one kernel; host/fftcc_plan.h (fftcc3d_kernel) says which
+// window each serves, and every launcher refuses the others' with hipErrorInvalidValue.
 // ---- fftcc3d_fused.hip -----------------------------------------------------
-// all of FFTCC3D::compute(POI3D*) in one kernel for 32 x 32 x 32 windows (radius 16)
-bool fftcc3d_fused_supported(int rx, int ry, int rz);
+// 32 x 32 x 32 windows (Fused32)
 hipError_t launch_fftcc3d_fused(const Fftcc3dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 #if OC_BUILD_AB
-// fftcc3d_fused_r5.hip (A/B build): the decomposition of rounds 1 - 5.  needs_clamped: fftcc3d_fused_flag_bytes(count) bytes of device
+// fftcc3d_fused_r5.hip (A/B build, Fused32R5): the decomposition of rounds 1 - 5.  needs_clamped: fftcc3d_fused_flag_bytes(count) bytes of device
 // scratch (its first launch flags the POIs whose windows are clamped at a volume border and raises one "any" word behind the flags,
 // its second one computes those -- and returns at once when the word is 0)
 size_t fftcc3d_fused_flag_bytes(size_t count);
@@ -313,22 +318,19 @@ hipError_t launch_fftcc3d_fused_r5(const Fftcc3dParams& p, float* pois, int stri
 #endif
 
 // ---- fftcc3d_fusedn.hip ----------------------------------------------------
-// the same for cubic windows of side 8 ... 26 (radius 4 ... 13): the complex volume stays in LDS between the axis passes
-bool fftcc3d_fusedn_supported(int rx, int ry, int rz);
+// small cubic windows (Cube): the complex volume stays in LDS between the axis passes
 hipError_t launch_fftcc3d_fusedn(const Fftcc3dParams& p, float* pois, int stride_floats, size_t count, bool xcd,
                                  hipStream_t stream);
 
 // ---- fftcc3d_box.hip ---------------------------------------------------------
-// the same for NON-cubic windows with every radius in 4 ... 16 whose complex volume fits the LDS: ONE kernel, the three sides
-// are run-time values (each axis pass switches to the line transform of its length)
-bool fftcc3d_box_supported(int rx, int ry, int rz);
+// NON-cubic windows whose complex volume fits the LDS (Box; fftcc3d_box_lds_bytes): ONE kernel, the three sides are run-time
+// values (each axis pass switches to the line transform of its length)
 hipError_t launch_fftcc3d_box(const Fftcc3dParams& p, float* pois, int stride_floats, size_t count, bool xcd, hipStream_t stream);
 
 // ---- fftcc3d_planes.hip / fftcc3d_planesb.hip -------------------------------
-// the same for cubic windows of side 28 ... 64 (except 32): one persistent 512-thread workgroup per scratch slot, the complex
-// volume passes through a private N^3 scratch volume between the in-LDS plane transforms and the z pass
-bool fftcc3d_planes_supported(int rx, int ry, int rz);
-size_t fftcc3d_planes_scratch_bytes(int radius, int blocks);
+// large cubic windows (Planes): one persistent 512-thread workgroup per scratch slot, the complex volume passes through a private
+// N^3 scratch volume between the in-LDS plane transforms and the z pass.  blocks: fftcc3d_planes_blocks, scratch:
+// fftcc3d_planes_scratch_bytes
 hipError_t launch_fftcc3d_planes(const Fftcc3dParams& p, float* pois, int stride_floats, size_t count, void* scratch, int blocks,
                                  hipStream_t stream);
 

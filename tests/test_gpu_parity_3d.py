@@ -8,6 +8,7 @@ the reference itself: its DVC example volumes are not in the mount.
 import numpy as np
 import pytest
 
+from fftcc_plan_model import box_kernel_takes as _box_kernel_takes
 from icgn3d_launch_shape import SWEEP_RADII
 
 pytestmark = pytest.mark.gpu
@@ -218,11 +219,6 @@ BOX_RADII = [(4, 5, 6), (6, 4, 5), (5, 6, 4), (7, 8, 9), (9, 7, 8), (8, 9, 7), (
              (11, 12, 13), (13, 11, 12), (12, 13, 11), (14, 4, 15), (15, 14, 4), (4, 15, 14), (16, 4, 4), (4, 16, 4), (4, 4, 16),
              (16, 16, 4), (4, 16, 16), (16, 4, 16), (16, 16, 8), (8, 16, 16), (16, 8, 16), (12, 12, 16), (16, 12, 12), (6, 8, 10),
              (13, 13, 4), (16, 15, 9), (13, 14, 15)]
-
-
-def _box_kernel_takes(rx, ry, rz):
-    """fftcc3d_box_supported(): the [2rx][2ry][2rz + 1] complex volume and the kernel's tables within 160 KB of LDS."""
-    return 2 * rx * 2 * ry * (2 * rz + 1) * 8 + 6 * 32 * 4 + 3 * 16 * 4 <= 160 * 1024
 
 
 @pytest.mark.parametrize("r", BOX_RADII)
