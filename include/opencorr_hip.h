@@ -324,8 +324,11 @@ int oc_hip_get_devices(const oc_hip_engine* engine, int* device_ids, int capacit
 int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** device_ptr, size_t* block_bytes);
 
 /* Knobs.  Every key but "arith_fma", "arith_onepass" and "arith_onepass3d" selects among kernels that compute BIT-IDENTICAL results; unknown keys and values
- * outside the stated range fail with OC_HIP_ERR_INVALID, values this build does not contain with OC_HIP_ERR_UNSUPPORTED.
- *   "arith_fma"       ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 only (other engines refuse 1).  0 (default): every
+ * outside a key's range fail with OC_HIP_ERR_INVALID; values this build does not contain, and non-zero values on an engine kind
+ * the key does not belong to, with OC_HIP_ERR_UNSUPPORTED.  The default of every key, its range, the engine kinds that may set
+ * it and the values only the A/B build of the library accepts are stated ONCE, as a table: opencorr_amd/csrc/host/engine_tuning.h
+ * (the initialisers of EngineTuning, the rows of kTuningKeys).  What the keys do:
+ *   "arith_fma"       ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 only (and the descriptor matcher).  0: every
  *                     multiply and add of the solver rounds on its own -- the reference built for baseline x86-64; GPU ==
  *                     oracle OC_ORDER_LANES bit for bit.  1: every PER-SAMPLE multiply-add is one fused multiply-add -- what a
  *                     compiler with FMA hardware makes of the reference's source expressions (src/oc_cubic_bspline.cpp:159-177,
@@ -335,7 +338,7 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     identical iteration counts, |d u, v, w| <= 1e-4 and |d ZNCC| <= 1e-5 (all BASELINE configs:
  *                     tests/test_gpu_fullsize.py).  Kernel time on one MI355X: ICGN2D1 -3 ... -9 %, ICGN2D2 -13 ... -17 %,
  *                     ICGN3D1 -5 ... -7 %.  The once-per-POI dense algebra is never fused
- *   "arith_onepass"   ICGN2D1 / ICGN2D2 only (every other engine refuses 1 with OC_HIP_ERR_UNSUPPORTED and accepts 0).  0 (default):
+ *   "arith_onepass"   ICGN2D1 / ICGN2D2 only.  0:
  *                     the contract "arith_fma" selects.  1: the ONE-PASS arithmetic contract (icgn2d_onepass.hip) -- an iteration is
  *                     one sweep over the warped subset with 3 + DOF running sums of e' = g (t - c) - r~ (c, g: mean and scale of the
  *                     previous iteration) and no target array; mean, norm, ZNSSD and the numerator are recovered from the sums
@@ -354,8 +357,7 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     SLOWER -- ICGN2D1 on config B 3.39 against 3.16 ms (x 1.07), ICGN2D2 on config C 3.66 against 3.17 ms
  *                     (x 1.15); against "arith_fma" = 1 as it ships, i.e. served by the set-up cache on repeated calls over one
  *                     reference, x 1.18 and x 1.41.  The contract is an option kept for its arithmetic, not a faster path
- *   "arith_onepass3d" ICGN3D1 only (every other engine refuses 1 with OC_HIP_ERR_UNSUPPORTED and accepts 0; ICGN3D1 in turn refuses
- *                     "arith_onepass" = 1 and names this key).  0 (default): the contract "arith_fma" selects.  1: the ONE-PASS
+ *   "arith_onepass3d" ICGN3D1 only (which in turn refuses "arith_onepass" = 1 and names this key).  0: the contract "arith_fma" selects.  1: the ONE-PASS
  *                     arithmetic contract carried to DVC (icgn3d_onepass.hip) -- the tap sweep of an iteration forms, per sample,
  *                     e' = g (t - c) - r~ and adds it to 3 + 12 running sums; no warped sample is stored, no scratch is reserved,
  *                     and mean, norm, ZNSSD and the numerator are recovered from the sums after ONE block reduction (DESIGN.md
@@ -370,7 +372,7 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     "icgn3d_mapping" = 1 together with this key fails with OC_HIP_ERR_UNSUPPORTED.  NOT RUN ON AN MI355X YET:
  *                     neither the kernel's bits nor its time have been measured (tools/onepass3d_ab.py)
  *   "icgn2d_variant"  launch shape of the ICGN2D kernel (gather depth, LDS footprint, per-workgroup coordinate table, waves per
- *                     workgroup); -1 (default) lets the engine choose: 5 / 4 (6 / 12 DoF: coordinate table, lockstep sweeps,
+ *                     workgroup); -1 lets the engine choose: 5 / 4 (6 / 12 DoF: coordinate table, lockstep sweeps,
  *                     8-wave workgroups) for queues >= 32768 POIs of subsets up to 35 x 34 / 41 x 41, 2 / 3 (no table) below,
  *                     7 (target array only) for self-adaptive subsets from 27 passes up (2 / 3 below), 1 (single-wave
  *                     workgroups) for what fits nothing else.  10 / 11 (6 / 12 DoF): the lockstep sweeps in 4-WAVE workgroups, six /
@@ -381,10 +383,10 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     For queues >= 32768 POIs the automatic choice takes them in place of 5 / 4 wherever they apply.  0, 6, 8 (the split launch shape) and 9 (the workgroup's
  *                     coefficient band staged in LDS, icgn2d_band.hip) are measured losers that only the A/B build of the
  *                     library contains
- *   "icgn2d_xcd"      1 (default): workgroups of one XCD serve a contiguous range of the POI queue
- *   "icgn2d_tile_px"  side of the square image tiles the ICGN2D / NR2D1 queue is visited by (L1 / L2 locality; default 128;
- *                     0 = queue order; applied to queues >= 16384 POIs)
- *   "icgn2d_setup_cache"  1 (default): ICGN2D1 / ICGN2D2 keep the per-POI set-up of their big-queue launches (variants 10 / 11, 5 / 4) --
+ *   "icgn2d_xcd"      1: workgroups of one XCD serve a contiguous range of the POI queue
+ *   "icgn2d_tile_px"  side of the square image tiles the ICGN2D / NR2D1 queue is visited by (L1 / L2 locality; 0 = queue order;
+ *                     applied to queues >= 16384 POIs)
+ *   "icgn2d_setup_cache"  1: ICGN2D1 / ICGN2D2 keep the per-POI set-up of their big-queue launches (variants 10 / 11, 5 / 4) --
  *                     reference mean, norm and inverse Hessian: 152 + 8 B per POI at 6 DoF, 584 + 8 B at 12 -- from one compute()
  *                     to the next and start from it while reference, gradients, radii, arithmetic, count, stride and the
  *                     queue's (x, y) stay what they were: the sequence "overwrite the target in place, prepare_tar(), compute()"
@@ -392,7 +394,7 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     the next call rebuild it; the coordinates are compared on the device, no call waits for the host.
  *                     Centre offsets, self-adaptive radii, IC-LM and smaller queues never use it.  0: every call computes its
  *                     set-up.  Same bits either way (oc_hip_icgn2d_setup_cache_last tells which way a call went)
- *   "icgn2d_int_first"  1 (default): while the warp of an ICGN2D1 / ICGN2D2 POI is an INTEGER TRANSLATION -- integral x, y, u, v and
+ *   "icgn2d_int_first"  1: while the warp of an ICGN2D1 / ICGN2D2 POI is an INTEGER TRANSLATION -- integral x, y, u, v and
  *                     zero gradients: the first iteration of every FFTCC2D guess -- the interpolation sweep reads each sample's
  *                     value from a value plane that prepare() / prepare_tar() store behind the coefficient table (the
  *                     interpolant at every pixel's own position, evaluated by the sweep's own polynomial code at zero
@@ -402,7 +404,7 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     (the behaviour before the plane existed).  Same bits either way, NaN / Inf pixels included
  *                     (tests/test_gpu_int_first.py); the key exists for that comparison and for measurements
  *   "icgn2d_split_chunks"  A/B build, variant 8 only: chunks of the two-stream pipeline (0 = the two kernels back to back)
- *   "fftcc2d_fused"   1 (default): single-kernel FFTCC2D (register / LDS FFT) for EVERY window with both radii in 4 ... 32 (even
+ *   "fftcc2d_fused"   1: single-kernel FFTCC2D (register / LDS FFT) for EVERY window with both radii in 4 ... 32 (even
  *                     sides 8 ... 64): a template instance per square side and for the 42 rectangular pairs (radius_x !=
  *                     radius_y) out of sides 16, 20, 24, 32, 40, 48, 64, one kernel with run-time sides (fftcc2d_rect.hip) for
  *                     every other rectangular pair; larger windows run the rocFFT pipeline.  0: rocFFT pipeline always.  2: as
@@ -410,31 +412,30 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  *                     the 32 x 32 kernel runs its body without the scalar row stepping of integral POIs and with a full complex
  *                     last inverse pass (the kernel before those two changes); 4 / 5: with the first / the second of the two
  *                     alone (A/B switches: same integers, ZNCC of 3 and 4 bit-identical)
- *   "fftcc3d_fused"   1 (default): single-kernel FFTCC3D for every cubic window of even side 8 ... 64 (radius 4 ... 32): LDS kernel
+ *   "fftcc3d_fused"   1: single-kernel FFTCC3D for every cubic window of even side 8 ... 64 (radius 4 ... 32): LDS kernel
  *                     up to 26^3, register kernel at 32^3, plane-wise kernel for 28^3 ... 64^3; and for every NON-cubic window
  *                     with all three radii in 4 ... 16 whose complex volume [2rx][2ry][2rz + 1] fits 160 KB of LDS (one kernel,
  *                     sides as run-time values: fftcc3d_box.hip); other non-cubic windows and larger sides run the rocFFT
  *                     pipeline.  0: rocFFT pipeline always.  2 (A/B build of the library only): as 1, but 32^3 windows run the
  *                     kernel of rounds 1 - 5 (fftcc3d_fused_r5.hip: same integers, ZNCC within 1e-6, 1.45 x the time)
- *   "fftcc3d_planes_blocks"  persistent workgroups (= private scratch volumes) of the plane-wise FFTCC3D kernel; 0 (default) = 256
- *   "fftcc3d_tile_vox"  FFTCC3D single-kernel paths: queues >= 2048 POIs are visited in cubic blocks of this many voxels
- *                     (default 64; 0 = queue order; >= 8)
- *   "icgn3d_tile_vox" the same for ICGN3D1 (default 64; 0 = queue order; >= 8)
- *   "icgn3d_mapping"  0 (default, the only value the shipped library accepts): sample s of a subvolume is owned by thread
+ *   "fftcc3d_planes_blocks"  persistent workgroups (= private scratch volumes) of the plane-wise FFTCC3D kernel; 0 = 256 of them
+ *   "fftcc3d_tile_vox"  FFTCC3D single-kernel paths: queues >= 2048 POIs are visited in cubic blocks of this many voxels (0 = queue order)
+ *   "icgn3d_tile_vox" the same for ICGN3D1
+ *   "icgn3d_mapping"  0: sample s of a subvolume is owned by thread
  *                     s mod 512 (icgn3d.hip; oracle OC_ORDER_LANES, lanes = 512); 1 (A/B build): one half-wave per subvolume row
  *                     (oracle OC_ORDER_ROWS; 12 - 25 % slower; no fused-arithmetic form)
- *   "single_combine"  1 (default): concurrent compute_one calls on an engine are combined into one launch per batch; 0: every
+ *   "single_combine"  1: concurrent compute_one calls on an engine are combined into one launch per batch; 0: every
  *                     call is a launch of its own (the behaviour up to round 5).  Same bits either way.
  *   "host_chunk"      POIs per chunk of the host-queue pipeline (copies of one chunk overlap the kernels of its
- *                     neighbours); 0 = whole queue at once; default 65536
+ *                     neighbours); 0 = whole queue at once
  *   "group_allgather" 1: device groups leave the complete result queue on every member (see oc_hip_set_devices)
  *   "group_force_rccl" 1 (with "group_allgather"): an engine WITHOUT a group sends its DEVICE queues down the group path
  *                     as a group of one, whose all-gather is an ncclAllGather on a one-rank communicator (queue ->
  *                     oc_hip_group_queue(engine, 0)); fails instead of falling back when librccl is unusable.  Exists
  *                     so that the RCCL binding (dlopen, version check, ncclCommInitAll, ncclAllGather) can be executed
  *                     on a one-GPU machine
- *   "match_splits"    descriptor matcher only: parts the candidate range of the distance kernel is cut into; 0 (default) =
- *                     automatic (enough parts for two workgroups per CU), 1 ... 64 forced.  Same bits for every value.  The
+ *   "match_splits"    descriptor matcher only: parts the candidate range of the distance kernel is cut into; 0 = automatic
+ *                     (enough parts for two workgroups per CU), else that many.  Same bits for every value.  The
  *                     matcher also takes "arith_fma" (see oc_hip_matcher_create); every other engine refuses this key with
  *                     OC_HIP_ERR_UNSUPPORTED
  * A device group (oc_hip_set_devices) hands every key on to its members. */

@@ -30,7 +30,7 @@ AB_LIB = os.path.join(AB_LIBDIR, "libopencorr_hip_ab.so")
 HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "dic2d_device.h", "fft_device.h", "fftcc2d_fusedn_impl.h", "fftcc3d_planes_impl.h", "icgn3d_device.h", os.path.join("..", "..", "include", "opencorr_hip.h"),
            # host logic without HIP calls; in a subfolder, so that kernel_fingerprint()'s listing of csrc/ (no PMC record goes stale
            # from a host-only change) does not see them
-           os.path.join("host", "single_combiner.h"), os.path.join("host", "chunk_pipeline.h"),
+           os.path.join("host", "single_combiner.h"), os.path.join("host", "chunk_pipeline.h"), os.path.join("host", "engine_tuning.h"),
            # ... except these two, which KERNEL_SOURCES names: the variant list of the first decides which ICGN2D kernels get
            # instantiated, the lists of window sides of the second which FFTCC kernels
            os.path.join("host", "icgn2d_plan.h"), os.path.join("host", "fftcc_plan.h")]

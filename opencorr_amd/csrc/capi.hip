@@ -46,8 +46,6 @@ int create_engine(int kind, int rx, int ry, int rz, float conv, float stop, int 
     e->rz = rz;
     e->conv = conv;
     e->stop = stop;
-    // MI355X sweep (profiles/r01b_icgn2d*_variant_sweep.json): 12 DoF keeps more registers live, so
-    // the single-wave G = 4 variant wins there
     OC_HIP_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
     e->stream = e->own_stream;
     *out = e.release();
@@ -610,6 +608,26 @@ int oc_hip_icgn3d1_create(int rx, int ry, int rz, float conv, float stop, int de
     return create_engine(OC_HIP_ICGN3D1, rx, ry, rz, conv, stop, device, out);
 }
 
+// The one teardown of an engine's device-bound state (oc_hip_destroy; rehome), the engine's device being current: wait for its
+// work, destroy the events, synchronise and destroy the streams, free the buffers and plans -- the engine is left holding a
+// default DeviceState, without a stream.
+static void reset_device_state(oc_hip_engine* e) {
+    drain_engine(e);  // never through a caller's stream handle: it may be gone already
+    DeviceState& d = *e;
+    clear_events(e);
+    for (hipEvent_t ev : {d.order_ev, d.switch_ev, d.group_ev})
+        if (ev) (void)hipEventDestroy(ev);
+    for (const std::vector<hipEvent_t>* evs : {&d.chunk_done, &d.chunk_in, &d.split_ev})
+        for (hipEvent_t ev : *evs) (void)hipEventDestroy(ev);
+    for (hipStream_t st : {d.copy_stream, d.copy_in_stream, d.aux_stream})
+        if (st) {
+            (void)hipStreamSynchronize(st);
+            (void)hipStreamDestroy(st);
+        }
+    if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
+    d = DeviceState{};  // (the buffers, the plans and the image pair free what they hold as they are assigned over)
+}
+
 int oc_hip_destroy(oc_hip_engine* e) {
     if (!e) return OC_HIP_OK;
     DeviceScope device_scope;
@@ -620,21 +638,7 @@ int oc_hip_destroy(oc_hip_engine* e) {
     }
     e->replicas.clear();
     (void)hipSetDevice(e->device);
-    drain_engine(e);  // never through a caller's stream handle: it may be gone already
-    clear_events(e);
-    e->fft.destroy();
-    if (e->order_ev) (void)hipEventDestroy(e->order_ev);
-    if (e->switch_ev) (void)hipEventDestroy(e->switch_ev);
-    if (e->group_ev) (void)hipEventDestroy(e->group_ev);
-    for (hipEvent_t ev : e->chunk_done) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->chunk_in) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->split_ev) (void)hipEventDestroy(ev);
-    for (hipStream_t* st : {&e->copy_stream, &e->copy_in_stream, &e->aux_stream})
-        if (*st) {
-            (void)hipStreamSynchronize(*st);
-            (void)hipStreamDestroy(*st);
-        }
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+    reset_device_state(e);
     delete e;
     return OC_HIP_OK;
 }
@@ -773,78 +777,22 @@ int oc_hip_share_images(oc_hip_engine* e, oc_hip_engine* donor) {
     return OC_HIP_OK;
 }
 
-// Clone of an engine's configuration on another device (a group member)
+// A group member: an engine of the leader's kind on `device` with the leader's settings
 static int clone_engine(const oc_hip_engine* e, int device, oc_hip_engine** out) {
     OC_TRY(create_engine(e->kind, e->rx, e->ry, e->rz, e->conv, e->stop, device, out));
-    oc_hip_engine* r = *out;
-    r->is_replica = true;
-    r->lm_lambda = e->lm_lambda;
-    r->lm_alpha = e->lm_alpha;
-    r->lm_beta = e->lm_beta;
-    r->icgn2d_tile_px = e->icgn2d_tile_px;
-    r->icgn2d_variant = e->icgn2d_variant;
-    r->self_adaptive = e->self_adaptive;
-    r->icgn2d_xcd = e->icgn2d_xcd;
-    r->arith_fma = e->arith_fma;
-    r->arith_onepass = e->arith_onepass;
-    r->arith_onepass3d = e->arith_onepass3d;
-    r->icgn2d_split_chunks = e->icgn2d_split_chunks;
-    r->icgn2d_setup_cache = e->icgn2d_setup_cache;
-    r->icgn2d_int_first = e->icgn2d_int_first;
-    r->fftcc2d_fused = e->fftcc2d_fused;
-    r->fftcc3d_fused = e->fftcc3d_fused;
-    r->fftcc3d_planes_blocks = e->fftcc3d_planes_blocks;
-    r->icgn3d_mapping = e->icgn3d_mapping;
-    r->icgn3d_tile_vox = e->icgn3d_tile_vox;
-    r->fftcc3d_tile_vox = e->fftcc3d_tile_vox;
-    r->host_chunk = e->host_chunk;
-    r->group_allgather = e->group_allgather;
-    r->group_force_rccl = e->group_force_rccl;
+    (*out)->is_replica = true;
+    static_cast<ochip_host::EngineTuning&>(**out) = *e;
     return OC_HIP_OK;
 }
 
-// Moves an engine to another device: everything it holds on the old one is released (images included: the caller
-// sets them again, like after construction).
+// Moves an engine to another device: everything it holds on the old one is released (images and descriptors included: the
+// caller sets them again, like after construction).
 static int rehome(oc_hip_engine* e, int device) {
     int ndev = 0;
     OC_HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(OC_HIP_ERR_INVALID, "device %d out of range [0,%d)", device, ndev);
     OC_HIP_TRY(hipSetDevice(e->device));
-    drain_engine(e);
-    e->tail_marked = false;
-    clear_events(e);
-    e->fft.destroy();
-    e->fft.work_fwd.release();
-    e->fft.work_inv.release();
-    for (DevBuf* b : {&e->gx, &e->gy, &e->gz, &e->coef, &e->coef_gx, &e->coef_gy, &e->tmp, &e->poi_stage, &e->off_stage, &e->cursors,
-                      &e->perm, &e->tiles, &e->perm_slots, &e->split_scratch, &e->split_tmp, &e->prefilter_tmp, &e->st_box, &e->st_counts, &e->st_start, &e->st_cursor, &e->st_slots,
-                      &e->st_order, &e->st_recs, &e->st_fallback, &e->win, &e->freq, &e->norms, &e->flags, &e->group_mirror,
-                      &e->group_off_mirror, &e->setup_cache_recs, &e->setup_cache_xy, &e->setup_cache_word, &e->mt_desc[0], &e->mt_desc[1],
-                      &e->mt_idx[0], &e->mt_idx[1], &e->mt_best[0], &e->mt_best[1], &e->mt_second[0], &e->mt_second[1], &e->mt_part, &e->mt_keys,
-                      &e->mt_scan, &e->mt_pairs, &e->mt_counter})
-        b->release();
-    e->mt_count[0] = e->mt_count[1] = 0;  // (descriptors are set again, like the images)
-    e->mt_ext[0] = e->mt_ext[1] = nullptr;
-    e->setup_cache_valid = false;
-    e->setup_cache_last = 0;
-    e->img.reset();
-    e->ref_ready = e->tar_ready = false;
-    e->coef_has_val = false;
-    e->st_count = 0;
-    if (e->order_ev) { (void)hipEventDestroy(e->order_ev); e->order_ev = nullptr; }
-    if (e->switch_ev) { (void)hipEventDestroy(e->switch_ev); e->switch_ev = nullptr; }
-    if (e->group_ev) { (void)hipEventDestroy(e->group_ev); e->group_ev = nullptr; }
-    for (hipEvent_t ev : e->chunk_done) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->chunk_in) (void)hipEventDestroy(ev);
-    e->chunk_done.clear();
-    e->chunk_in.clear();
-    if (e->copy_stream) { (void)hipStreamDestroy(e->copy_stream); e->copy_stream = nullptr; }
-    if (e->copy_in_stream) { (void)hipStreamDestroy(e->copy_in_stream); e->copy_in_stream = nullptr; }
-    for (hipEvent_t ev : e->split_ev) (void)hipEventDestroy(ev);
-    e->split_ev.clear();
-    if (e->aux_stream) { (void)hipStreamSynchronize(e->aux_stream); (void)hipStreamDestroy(e->aux_stream); e->aux_stream = nullptr; }
-    (void)hipStreamDestroy(e->own_stream);
-    e->own_stream = nullptr;
+    reset_device_state(e);
     OC_HIP_TRY(hipSetDevice(device));
     e->device = device;
     OC_HIP_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
@@ -1022,99 +970,16 @@ int oc_hip_reset_stream(oc_hip_engine* e) {
     return switch_stream(e, e->own_stream, true);
 }
 
+static_assert(ochip_host::kTuningMatchMaxSplits == ochip::kMatchMaxSplits, "the range of \"match_splits\" is the matcher's limit");
+
+// The keys, their rules and the words of their refusals: host/engine_tuning.h
 int oc_hip_set_tuning(oc_hip_engine* e, const char* key, int value) {
     OC_TRY(check_engine(e));
     if (!key) return fail(OC_HIP_ERR_INVALID, "null tuning key");
     std::lock_guard<std::mutex> lock(e->mu);
-    const std::string k(key);
-    if (k == "icgn2d_variant") {
-        if (value < -1 || value >= ochip_host::kIcgn2dVariantCount)
-            return fail(OC_HIP_ERR_INVALID, "icgn2d_variant %d out of range [-1 (automatic), %d)", value, ochip_host::kIcgn2dVariantCount);
-        if (value >= 0 && !ochip_host::icgn2d_variant_built(value, OC_BUILD_AB != 0))
-            return fail(OC_HIP_ERR_UNSUPPORTED, "icgn2d_variant %d is an A/B partner that only the A/B build of the library contains "
-                                               "(python -m opencorr_amd.build --ab)", value);
-        e->icgn2d_variant = value;
-    } else if (k == "icgn2d_xcd" || k == "xcd") {
-        e->icgn2d_xcd = value != 0;
-    } else if (k == "arith_fma") {
-        if (value != 0 && !(e->is_icgn2d() || e->kind == OC_HIP_ICGN3D1 || e->is_matcher()))
-            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines and the descriptor matcher have a fused-arithmetic build");
-        e->arith_fma = value != 0;
-    } else if (k == "match_splits") {
-        // parts the candidate range of the descriptor matcher's distance kernel is cut into (0 = automatic; same bits for every value)
-        if (!e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "match_splits: the key of the descriptor matcher");
-        if (value < 0 || value > ochip::kMatchMaxSplits) return fail(OC_HIP_ERR_INVALID, "match_splits must be 0 (automatic) ... %d", ochip::kMatchMaxSplits);
-        e->mt_splits = value;
-    } else if (k == "arith_onepass") {
-        if (value != 0 && e->kind == OC_HIP_ICGN3D1)
-            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass: the key of the ICGN2D1 / ICGN2D2 engines; the one-pass build of ICGN3D1 has a "
-                                                "key of its own, arith_onepass3d");
-        if (value != 0 && !(e->kind == OC_HIP_ICGN2D1 || e->kind == OC_HIP_ICGN2D2))
-            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass: only the ICGN2D1 / ICGN2D2 engines have a one-pass build");
-        e->arith_onepass = value != 0;
-    } else if (k == "arith_onepass3d") {
-        if (value != 0 && e->kind != OC_HIP_ICGN3D1)
-            return fail(OC_HIP_ERR_UNSUPPORTED, "arith_onepass3d: only the ICGN3D1 engine has this one-pass build (ICGN2D1 / ICGN2D2: "
-                                                "arith_onepass)");
-        e->arith_onepass3d = value != 0;
-    } else if (k == "icgn2d_split_chunks") {
-#if !OC_BUILD_AB
-        // (the split launch shape, variant 8, exists in the A/B build only: the key would have no effect here -- ADVICE r5)
-        if (value != 0)
-            return fail(OC_HIP_ERR_UNSUPPORTED, "icgn2d_split_chunks belongs to icgn2d_variant 8, an A/B partner that only the A/B build of the "
-                                                "library contains (python -m opencorr_amd.build --ab)");
-#endif
-        if (value < 0 || value > 256) return fail(OC_HIP_ERR_INVALID, "icgn2d_split_chunks must be 0 (back to back) ... 256");
-        e->icgn2d_split_chunks = value;
-    } else if (k == "icgn2d_setup_cache") {
-        // 1 = the big-queue ICGN2D1 / ICGN2D2 launches keep their set-up records from call to call, 0 = every call computes them
-        e->icgn2d_setup_cache = value != 0;
-    } else if (k == "icgn2d_int_first") {
-        // 1 = an ICGN2D1 / ICGN2D2 sweep whose warp is an integer translation reads the table's value plane, 0 = every sweep gathers
-        // the coefficients and evaluates the polynomial (the kernel's behaviour before the plane existed; same bits)
-        e->icgn2d_int_first = value != 0;
-    } else if (k == "icgn2d_tile_px") {
-        if (value < 0 || (value > 0 && value < 16)) return fail(OC_HIP_ERR_INVALID, "icgn2d_tile_px must be 0 (off) or >= 16");
-        e->icgn2d_tile_px = value;
-    } else if (k == "fftcc2d_fused") {
-        // 3 = the 32 x 32 kernel's body without the fast row stepping and the real-output last pass, 4 / 5 = with the first /
-        // the second of them alone (A/B partners; every other window shape treats 3 ... 5 like 1)
-        e->fftcc2d_fused = (value >= 2 && value <= 5) ? value : (value != 0);
-    } else if (k == "fftcc3d_fused") {
-#if !OC_BUILD_AB
-        if (value == 2)
-            return fail(OC_HIP_ERR_UNSUPPORTED, "fftcc3d_fused = 2 (the 32^3 kernel of rounds 1 - 5) is an A/B partner that only the A/B build of the "
-                                                "library contains (python -m opencorr_amd.build --ab)");
-#endif
-        e->fftcc3d_fused = value == 2 ? 2 : (value != 0);
-    } else if (k == "fftcc3d_tile_vox") {
-        if (value < 0 || (value > 0 && value < 8)) return fail(OC_HIP_ERR_INVALID, "fftcc3d_tile_vox must be 0 (off) or >= 8");
-        e->fftcc3d_tile_vox = value;
-    } else if (k == "icgn3d_tile_vox") {
-        if (value < 0 || (value > 0 && value < 8)) return fail(OC_HIP_ERR_INVALID, "icgn3d_tile_vox must be 0 (off) or >= 8");
-        e->icgn3d_tile_vox = value;
-    } else if (k == "icgn3d_mapping") {
-#if !OC_BUILD_AB
-        if (value != 0)
-            return fail(OC_HIP_ERR_UNSUPPORTED, "icgn3d_mapping = 1 (the row mapping, measured 12 - 25 %% slower) is an A/B partner that only "
-                                               "the A/B build of the library contains (python -m opencorr_amd.build --ab)");
-#endif
-        e->icgn3d_mapping = value != 0;
-    } else if (k == "fftcc3d_planes_blocks") {
-        if (value < 0 || value > 4096) return fail(OC_HIP_ERR_INVALID, "fftcc3d_planes_blocks must be 0 (default) ... 4096");
-        e->fftcc3d_planes_blocks = value;
-    } else if (k == "single_combine") {
-        e->single_combine = value != 0;
-    } else if (k == "host_chunk") {
-        if (value < 0 || (value > 0 && value < 16384)) return fail(OC_HIP_ERR_INVALID, "host_chunk must be 0 (off) or >= 16384 POIs");
-        e->host_chunk = value;
-    } else if (k == "group_allgather") {
-        e->group_allgather = value != 0;
-    } else if (k == "group_force_rccl") {
-        e->group_force_rccl = value != 0;
-    } else {
-        return fail(OC_HIP_ERR_INVALID, "unknown tuning key '%s'", key);
-    }
+    const ochip_host::TuningResult set = ochip_host::tuning_set(*e, e->kind, key, value, OC_BUILD_AB != 0);
+    if (set.refusal == ochip_host::TuningRefusal::UnknownKey) return fail(set.status, "unknown tuning key '%s'", key);
+    if (set.refusal != ochip_host::TuningRefusal::None) return fail(set.status, set.words(), value);
     for (oc_hip_engine* r : e->replicas) OC_TRY(oc_hip_set_tuning(r, key, value));
     return OC_HIP_OK;
 }

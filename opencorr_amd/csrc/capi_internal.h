@@ -1,7 +1,7 @@
 // capi_internal.h -- what the translation units of the C-ABI (capi.hip: engines and entry points; capi_host.hip: the chunked
 // host-queue pipeline; capi_group.hip: device groups + the RCCL binding; capi_strain.hip: Strain / RegionFit and the reliable /
 // unreliable selection) share: the engine object, device buffers, error reporting, the stream / tail-event helpers.
-// host/*.h: host logic without HIP calls (the single-POI combiner, the chunk schedule and hand-off), standard headers only.
+// host/*.h: host logic without HIP calls (the tuning keys and settings, the single-POI combiner, the chunk schedule and hand-off).
 #pragma once
 #include "../../include/opencorr_hip.h"
 
@@ -23,6 +23,8 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 // RCCL: types and enumerators only -- the library itself is loaded with dlopen on first use (struct Rccl), and a
@@ -51,6 +53,7 @@ ncclResult_t ncclGetVersion(int* version);
 
 #include "oc_kernels.h"
 #include "host/chunk_pipeline.h"
+#include "host/engine_tuning.h"
 #include "host/single_combiner.h"
 
 namespace ochip_capi {
@@ -80,9 +83,18 @@ int fail(int code, const char* fmt, ...);
         if (rc__ != OC_HIP_OK) return rc__; \
     } while (0)
 
+// DevBuf, PinnedBuf and FftPlans free what they hold in their destructors: move-only, and a move leaves the source empty.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        DevBuf taken(std::move(o));  // (what this one held goes with `taken`)
+        std::swap(p, taken.p);
+        std::swap(bytes, taken.bytes);
+        return *this;
+    }
     ~DevBuf() { release(); }
     void release() {
         if (p) (void)hipFree(p);
@@ -109,6 +121,14 @@ struct DevBuf {
 struct PinnedBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        PinnedBuf taken(std::move(o));  // (what this one held goes with `taken`)
+        std::swap(p, taken.p);
+        std::swap(bytes, taken.bytes);
+        return *this;
+    }
     ~PinnedBuf() { release(); }
     void release() {
         if (p) (void)hipHostFree(p);
@@ -147,6 +167,17 @@ struct FftPlans {
     rocfft_plan fwd = nullptr, inv = nullptr;
     rocfft_execution_info info_fwd = nullptr, info_inv = nullptr;
     DevBuf work_fwd, work_inv;
+    FftPlans() = default;
+    FftPlans(FftPlans&& o) noexcept { *this = std::move(o); }
+    FftPlans& operator=(FftPlans&& o) noexcept {
+        if (this == &o) return *this;
+        destroy();
+        n0 = o.n0, n1 = o.n1, n2 = o.n2, chunk = std::exchange(o.chunk, 0);
+        fwd = std::exchange(o.fwd, nullptr), inv = std::exchange(o.inv, nullptr);
+        info_fwd = std::exchange(o.info_fwd, nullptr), info_inv = std::exchange(o.info_inv, nullptr);
+        work_fwd = std::move(o.work_fwd), work_inv = std::move(o.work_inv);
+        return *this;
+    }
     void destroy() {
         if (fwd) rocfft_plan_destroy(fwd);
         if (inv) rocfft_plan_destroy(inv);
@@ -159,16 +190,18 @@ struct FftPlans {
     ~FftPlans() { destroy(); }
 };
 
+template <class T> constexpr bool kMoveOnly = std::is_nothrow_move_constructible<T>::value && std::is_nothrow_move_assignable<T>::value &&
+                                            !std::is_copy_constructible<T>::value && !std::is_copy_assignable<T>::value;
+static_assert(kMoveOnly<DevBuf> && kMoveOnly<PinnedBuf> && kMoveOnly<FftPlans>, "a copy would free twice");
+
 void rocfft_init_once();   // capi.hip
 
 }  // namespace ochip_capi
 using namespace ochip_capi;
 
-struct oc_hip_engine {
-    int kind = 0;
-    int device = 0;
-    int rx = 0, ry = 0, rz = 0;
-    float conv = 0.001f, stop = 10.f;
+// Everything an engine holds that is bound to its device or to its streams.  reset_device_state (capi.hip) is the one teardown:
+// oc_hip_destroy ends with it, a move to another device (oc_hip_set_devices) starts from it -- a member added here is covered by both.
+struct DeviceState {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t order_ev = nullptr;  // orders the private stream behind the caller's default-stream work
@@ -206,19 +239,49 @@ struct oc_hip_engine {
         }
     } setup_cache_key;
     bool setup_cache_valid = false;          // the records belong to setup_cache_key
-    unsigned long long ref_generation = 0;   // bumped by set_images / share_images / prepare_ref: the reference or its gradients changed
     unsigned setup_cache_epoch = 0;          // one per cached launch; the coordinate check stamps the word with it
     int setup_cache_last = 0;                // last run_icgn2d: 0 = went around the cache, 1 = fill (host's decision), 2 = the device word decided
-    int icgn2d_int_first = 1;                // "icgn2d_int_first" tuning key: 0 = every interpolation sweep is the full one (icgn2d.hip kIntSweep)
     bool coef_has_val = false;               // 2D: the value plane (im.count() floats) lies behind the 16 coefficient floats per pixel in `coef`
-    int icgn2d_setup_cache = 1;              // "icgn2d_setup_cache" tuning key: 0 = every call computes its set-up (the behaviour before the cache)
     DevBuf split_scratch, split_tmp; // oc_hip_split_reliable / oc_hip_merge_recovered (poi_split.hip)
-    // Strain (src/oc_strain.cpp:31-46: radius, min neighbours; ZNCC threshold 0.9, Cauchy approximation)
-    float st_radius = 0.f, st_zncc = 0.9f;
-    int st_nmin = 0, st_approx = 1, st_ndim = 0;
+    // Strain
     size_t st_count = 0;  // queue length the grid was prepared for (0 = not prepared)
     ochip::StrainGrid st_grid{};
     DevBuf st_box, st_counts, st_start, st_cursor, st_slots, st_order, st_recs, st_fallback;
+    DevBuf cal_map_x, cal_map_y, cal_stage;  // Calibration: the undistortion map
+    // Descriptor matcher: side 0 = reference, 1 = target.  HOST descriptors are copied into mt_desc, DEVICE ones are used in place (mt_ext).
+    size_t mt_count[2] = {0, 0};
+    const float* mt_ext[2] = {nullptr, nullptr};
+    DevBuf mt_desc[2], mt_idx[2], mt_best[2], mt_second[2];   // [direction] for the results: 0 = ref -> tar, 1 = tar -> ref
+    DevBuf mt_part, mt_keys, mt_scan, mt_pairs, mt_counter;
+    // FFTCC working set
+    FftPlans fft;
+    DevBuf win, freq, norms, flags;
+    // host-queue pipeline (compute_host): the queue travels in chunks, copies of one chunk overlap the kernels of
+    // its neighbours; one event per chunk orders the copy-out stream behind the kernels
+    hipStream_t copy_stream = nullptr, copy_in_stream = nullptr;
+    // icgn2d variant 8 with "icgn2d_split_chunks" >= 2: the set-up kernels run on this second stream, one or two chunks ahead
+    // of the iteration kernels on the engine's stream, so that workgroups of both kinds are resident together
+    hipStream_t aux_stream = nullptr;
+    std::vector<hipEvent_t> split_ev;
+    std::vector<hipEvent_t> chunk_done, chunk_in;
+    DevBuf group_mirror;         // device groups: full-size copy of a DEVICE queue (members other than the leader work in theirs)
+    DevBuf group_off_mirror;
+    size_t group_mirror_block = 0;  // bytes per member block of the last all-gathered queue
+    hipEvent_t group_ev = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // profiling
+};
+
+// The engine: its settings (host/engine_tuning.h: what oc_hip_set_tuning, set_self_adaptive and set_damping write, and what a
+// group member takes from its leader as a whole), its device-bound state, and what belongs to neither.
+struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
+    int kind = 0;
+    int device = 0;
+    int rx = 0, ry = 0, rz = 0;
+    float conv = 0.001f, stop = 10.f;
+    unsigned long long ref_generation = 0;   // bumped by set_images / share_images / prepare_ref: the reference or its gradients changed
+    // Strain (src/oc_strain.cpp:31-46: radius, min neighbours; ZNCC threshold 0.9, Cauchy approximation)
+    float st_radius = 0.f, st_zncc = 0.9f;
+    int st_nmin = 0, st_approx = 1, st_ndim = 0;
     // Calibration (src/oc_calibration.h:47-97): the 13 + 6 numbers, the four small matrices (host code, row-major), the
     // undistortion map on the device.  Stereovision (src/oc_stereovision.h): the two cameras (handles the caller keeps alive,
     // like the reference's Calibration pointers) and the fundamental matrix.  Handles of these two kinds are created without
@@ -227,52 +290,12 @@ struct oc_hip_engine {
     float cal_K[9] = {}, cal_R[9] = {}, cal_T[3] = {}, cal_P[12] = {};
     float cal_conv = 0.001f;
     int cal_iter = 40, cal_h = 0, cal_w = 0;
-    DevBuf cal_map_x, cal_map_y, cal_stage;
     oc_hip_engine* stereo_cam[2] = {nullptr, nullptr};
     float stereo_F[9] = {};
-    // Descriptor matcher (capi_match.hip; SIFT3D::bruteforceMatch and the two match modes, src/oc_sift.cpp:625-674, 1251-1487):
-    // side 0 = reference, 1 = target.  HOST descriptors are copied into mt_desc, DEVICE ones are used in place (mt_ext).
-    int mt_dim = 0, mt_splits = 0;   // "match_splits" tuning key: 0 = automatic, 1 ... 64 forced
+    // Descriptor matcher (capi_match.hip; SIFT3D::bruteforceMatch and the two match modes, src/oc_sift.cpp:625-674, 1251-1487)
+    int mt_dim = 0;
     float mt_ratio = 0.f;
-    size_t mt_count[2] = {0, 0};
-    const float* mt_ext[2] = {nullptr, nullptr};
-    DevBuf mt_desc[2], mt_idx[2], mt_best[2], mt_second[2];   // [direction] for the results: 0 = ref -> tar, 1 = tar -> ref
-    DevBuf mt_part, mt_keys, mt_scan, mt_pairs, mt_counter;
-    float lm_lambda = 100.f, lm_alpha = 0.1f, lm_beta = 10.f;  // DampingParameter defaults, src/oc_iclm.h:33-38
-    int icgn2d_tile_px = 128;  // 0 = visit the queue in its own order (64 until round 3; 128 suits the lockstep sweeps: 3.29 vs 3.34 ms)
-    // FFTCC working set
-    FftPlans fft;
-    DevBuf win, freq, norms, flags;
-    // kernel selection (oc_hip_set_tuning); every choice computes the same bits
-    int icgn2d_variant = -1;  // -1 = automatic (run_icgn2d; MI355X sweeps), else the variant oc_hip_set_tuning chose
-    bool self_adaptive = false;  // DIC::setSelfAdaptive
-    int icgn2d_xcd = 1;
-    // ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1: 0 = every multiply and add of the solver rounds on its own (oracle
-    // OC_ORDER_LANES; the reference built for baseline x86-64), 1 = the per-sample multiply-adds are fused (oc_device.h
-    // OC_FMA; oracle OC_ORDER_LANES_FMA) -- the only tuning key that changes result bits (by rounding, inside north_star's
-    // tolerance: DESIGN.md section 3)
-    int arith_fma = 0;
-    int arith_onepass = 0;       // "arith_onepass" tuning key (ICGN2D1 / ICGN2D2): the one-pass arithmetic contract, icgn2d_onepass.hip
-    int arith_onepass3d = 0;     // "arith_onepass3d" tuning key (ICGN3D1): the one-pass arithmetic contract, icgn3d_onepass.hip
-    int fftcc2d_fused = 1;    // single-kernel FFTCC2D when the window is 32 x 32
-    int fftcc3d_fused = 1;    // single-kernel FFTCC3D for cubic windows of side 8 ... 64 (three kernels by size)
-    int fftcc3d_planes_blocks = 0;  // persistent workgroups (= scratch volumes) of the plane-wise kernel; 0 = 256
-    int fftcc3d_tile_vox = 64; // FFTCC3D single-kernel paths: queues of >= 2048 POIs are visited in cubic blocks of this many voxels (0 = queue order)
-    int icgn3d_tile_vox = 64; // ICGN3D1: queues of >= 2048 POIs are visited in cubic blocks of this many voxels (0 = queue order; config E: 78.8 -> 75.5 ms, profiles/r4g_icgn3d1_ab_block_schedule.txt)
-    int icgn3d_mapping = 0;   // ICGN3D1: 0 = sample s owned by thread s mod 512 (icgn3d.hip; oracle order OC_ORDER_LANES) -- the default:
-                              // 1 = one half-wave per subvolume row (icgn3d_rows.hip; OC_ORDER_ROWS), built and measured in round 4:
-                              // bit-exact against its own order, 12 - 25 % SLOWER -- kept as the A/B partner
-    // host-queue pipeline (compute_host): the queue travels in chunks, copies of one chunk overlap the kernels of
-    // its neighbours; one event per chunk orders the copy-out stream behind the kernels
-    hipStream_t copy_stream = nullptr, copy_in_stream = nullptr;
-    // icgn2d variant 8 with "icgn2d_split_chunks" >= 2: the set-up kernels run on this second stream, one or two chunks ahead
-    // of the iteration kernels on the engine's stream, so that workgroups of both kinds are resident together
-    hipStream_t aux_stream = nullptr;
-    std::vector<hipEvent_t> split_ev;
-    int icgn2d_split_chunks = 0;
-    std::vector<hipEvent_t> chunk_done, chunk_in;
     ochip_host::ChunkHandoff chunk_handoff;  // the copy-out thread sleeps here until the next chunk has been handed over
-    int host_chunk = 65536;  // POIs per chunk ("host_chunk" tuning key; 0 = the whole queue at once)
     std::atomic<unsigned> single_calls{0};  // compute(POI*) calls on this engine (one hint on stderr when a caller loops over them)
     // Combining front end of compute(POI*) (host/single_combiner.h): callers that arrive while a launch is in flight are queued;
     // one of them (the leader) hands the whole batch to the engine as ONE queue (serve_single_batch, capi.hip).
@@ -285,7 +308,6 @@ struct oc_hip_engine {
     };
     using SingleCombiner = ochip_host::SingleCombiner<SinglePoi>;
     SingleCombiner single_combiner;
-    int single_combine = 1;                      // "single_combine" tuning key: 0 = every call a launch of its own (the round-5 behaviour)
     std::atomic<unsigned long long> single_batches{0}, single_batched_pois{0}, single_engine_ns{0};   // (engine_ns: time inside the engine calls)
     PinnedBuf single_buf, single_off;            // the leader's contiguous, page-locked copy of a batch's records (and offsets)
     // device group (oc_hip_set_devices): this engine leads, replicas[i] is a full engine of the same kind on
@@ -293,16 +315,8 @@ struct oc_hip_engine {
     std::vector<oc_hip_engine*> replicas;
     std::vector<int> group_devices;
     bool is_replica = false;
-    int group_allgather = 0;     // DEVICE queues: leave the complete result queue in every member's mirror
-    int group_force_rccl = 0;    // the all-gather goes through RCCL even for a group of ONE (a one-rank communicator)
-    DevBuf group_mirror;         // full-size copy of a DEVICE queue (members other than the leader work in theirs)
-    DevBuf group_off_mirror;
-    size_t group_mirror_block = 0;  // bytes per member block of the last all-gathered queue
-    hipEvent_t group_ev = nullptr;
     void* rccl_comm = nullptr;   // ncclComm_t of this member (group_allgather with distinct devices)
-    // profiling
-    bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    bool prof = false;           // profiling
     mutable std::mutex mu;
 
     bool is_matcher() const { return kind == OC_HIP_MATCHER; }

@@ -202,6 +202,39 @@ def test_group_on_distinct_devices(case2d):
         assert np.array_equal(_bits(host.reshape(-1, floats)[:n]), _bits(want)), member
 
 
+def test_engine_moves_between_devices():
+    """set_devices([1]) and back to [0] on single engines: everything bound to the old device -- tables, staging, the set-up
+    cache's records, rocFFT plans and their work buffers (FFTCC2D at r = 33 runs the rocFFT pipeline) -- is released and built
+    again on the new one; the three result queues are equal byte for byte.  Needs >= 2 GPUs."""
+    import opencorr_amd
+    from opencorr_amd import capi, synth
+    if capi.device_count() < 2:
+        pytest.skip("one GPU visible")
+    ref, tar = synth.speckle_pair_2d(96, 96, seed=5)
+    xs, ys = synth.poi_grid_2d(96, 96, 8, 8, 12)
+    pois = opencorr_amd.make_pois2d(xs, ys)
+    assert len(pois) == 64
+    big_ref, big_tar = synth.speckle_pair_2d(160, 160, seed=6)
+    bx, by = synth.poi_grid_2d(160, 160, 4, 2, 40)
+    big_pois = opencorr_amd.make_pois2d(bx, by)
+    assert len(big_pois) == 8
+    icgn = opencorr_amd.ICGN2D1(8, 8, 0.001, 10)
+    fftcc = opencorr_amd.FFTCC2D(33, 33)
+    got = []
+    for device in (0, 1, 0):
+        if got:
+            icgn.set_devices([device])
+            fftcc.set_devices([device])
+        assert icgn.devices() == [device] == fftcc.devices()
+        icgn.set_images(ref, tar)
+        icgn.prepare()
+        fftcc.set_images(big_ref, big_tar)
+        fftcc.prepare()
+        got.append((icgn.compute(pois.copy()).tobytes(), fftcc.compute(big_pois.copy()).tobytes()))
+    assert got[0] == got[1] == got[2]
+    assert got[0][0] != pois.tobytes() and got[0][1] != big_pois.tobytes()   # (both engines wrote their results)
+
+
 def test_rccl_allgather_on_a_one_rank_communicator(case2d):
     """The RCCL binding itself -- dlopen of librccl, the version check, ncclCommInitAll, ncclGroupStart/End and an
     ncclAllGather of ncclUint8 blocks -- executed on ONE GPU: with "group_force_rccl" a lone engine's DEVICE queue goes
