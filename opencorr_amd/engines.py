@@ -92,7 +92,9 @@ class _Engine:
         stream of its own: the donor's images may still be in flight on that stream, and ``prepare()`` receives no tensor
         it could take the stream from -- on its private stream it would read them too early."""
         capi.check(capi.lib().oc_hip_share_images(self._h, donor._h))
-        self._keep = [donor]
+        # the pair is the borrower's from here on (the engine holds its own reference): device images used in place must
+        # outlive the donor's next set_images too
+        self._keep = [donor] + list(donor._keep)
         self.shape = donor.shape
         if not self._stream_pinned and not getattr(donor, "_on_private_stream", True):
             s = donor._auto_stream

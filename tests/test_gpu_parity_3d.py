@@ -10,6 +10,7 @@ import pytest
 
 from fftcc_plan_model import box_kernel_takes as _box_kernel_takes
 from icgn3d_launch_shape import SWEEP_RADII
+from shape_cases import SHAPES3D_MIN
 
 pytestmark = pytest.mark.gpu
 
@@ -41,11 +42,12 @@ def test_prepare3d_fields_bit_exact(volumes):
     assert np.array_equal(_bits(icgn.read_field("coef")), _bits(coef))
 
 
-@pytest.mark.parametrize("shape", [(37, 41, 43), (20, 130, 17), (65, 16, 520), (37, 41, 44), (16, 18, 16), (61, 15, 260)])
+@pytest.mark.parametrize("shape", [(37, 41, 43), (20, 130, 17), (65, 16, 520), (37, 41, 44), (16, 18, 16), (61, 15, 260)] + SHAPES3D_MIN)
 def test_prepare3d_odd_shapes_bit_exact(shape):
     """The walking prepare kernels on shapes that exercise their tails: runs that are no multiple of 15 / 64, rows that
     are not 16-byte aligned (scalar kernels) and rows that are (16-byte kernels), more than one x block / row segment,
-    dimensions barely above the 15-voxel minimum of the engine."""
+    dimensions barely above the 15-voxel minimum of the engine -- and at it (shape_cases.SHAPES3D_MIN: every side once, with the
+    scalar and the 16-byte kernels)."""
     import opencorr_amd
     import oracle
     rng = np.random.default_rng(sum(shape))
