@@ -138,10 +138,13 @@ int run_fftcc_rocfft(oc_hip_engine* e, float* d_pois, int stride_f, size_t count
     return OC_HIP_OK;
 }
 
+int check_fftcc2d_limits(const ImagePair& im);   // (with the other image limits, below)
+
 int run_fftcc2d(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
     using ochip_host::Fftcc2dKernel;
     if (!e->img || e->img->ndim != 2) return fail(OC_HIP_ERR_INVALID, "FFTCC2D: set_images2d has not been called");
     const ImagePair& im = *e->img;
+    OC_TRY(check_fftcc2d_limits(im));   // (before anything is reserved or enqueued)
     const ochip::Fftcc2dParams P = {im.ref_ptr(), im.tar_ptr(), im.dy, im.dx, e->rx, e->ry};
     const Fftcc2dKernel kernel = ochip_host::fftcc2d_kernel(e->rx, e->ry, e->fftcc2d_fused);
     if (kernel == Fftcc2dKernel::RocFft) {
@@ -204,6 +207,17 @@ int check_image2d_limits(const char* who, const ImagePair& im, unsigned long lon
     if ((unsigned long long)im.dy * (unsigned long long)im.dx > max_pixels || im.dx >= (1 << 22) || im.dy >= (1 << 22))
         return fail(OC_HIP_ERR_UNSUPPORTED, "%s: image %d x %d exceeds the engine's limit of %llu pixels (width, height < 2^22)", who,
                     im.dx, im.dy, max_pixels);
+    return OC_HIP_OK;
+}
+
+// FFTCC2D reads the two images alone, 4 B per pixel, through the same descriptors: `(row * width + column) << 2` with a
+// 24-bit multiply (fftcc2d_fused.hip, fftcc2d_fusedn_impl.h and the prime / pair kernels built on it) stays below 2^32
+// up to 2^30 pixels and is exact while both sides are below 2^24.  One rule for every FFTCC2D kernel, the ones that
+// address with size_t (fftcc2d_rect.hip, the rocFFT gather) included: a window must not decide whether an image is taken.
+int check_fftcc2d_limits(const ImagePair& im) {
+    if ((unsigned long long)im.dy * (unsigned long long)im.dx > (1ull << 30) || im.dx >= (1 << 24) || im.dy >= (1 << 24))
+        return fail(OC_HIP_ERR_UNSUPPORTED, "FFTCC2D: image %d x %d exceeds the engine's limit of %llu pixels (width, height < 2^24)", im.dx,
+                    im.dy, 1ull << 30);
     return OC_HIP_OK;
 }
 
@@ -1082,6 +1096,9 @@ static int compute_impl(oc_hip_engine* e, void* pois, const float* offsets, size
     if (offsets && e->kind != OC_HIP_ICGN2D1 && e->kind != OC_HIP_ICGN2D2)
         return fail(OC_HIP_ERR_INVALID, "center offsets are an ICGN2D1/ICGN2D2 feature (src/oc_icgn.h:75-76,130-131)");
     std::lock_guard<std::mutex> lock(e->mu);
+    // (FFTCC2D's image limit is known before anything moves: refused before a host queue is staged or an event recorded;
+    // run_fftcc2d asks again for the paths that do not come through here)
+    if (e->kind == OC_HIP_FFTCC2D && e->img && e->img->ndim == 2) OC_TRY(check_fftcc2d_limits(*e->img));
     TailGuard tail(e);  // also the error exits leave the enqueued work covered by the tail event
     // a queue of a few POIs is not worth waking the other devices for; "group_force_rccl" sends a lone engine's DEVICE
     // queue down the group path as well (a group of one, whose all-gather is a one-rank ncclAllGather)

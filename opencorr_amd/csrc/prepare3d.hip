@@ -327,19 +327,20 @@ hipError_t launch_bspline3d_prefilter(const float* vol, int dz, int dy, int dx, 
     if (rows_of_float4(dx, vol, coef, tmp)) {
         hipLaunchKernelGGL(bspline3d_prefilter_x4_kernel, dim3((dx + 255) / 256, (dy + 3) / 4, dz), dim3(256), 0, stream, vol, coef, dz, dy,
                            dx);
-        (void)hipGetLastError();
+        // (a launch that was refused leaves its pass undone: the error goes to the caller, not to the next launch's report)
+        if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
         hipLaunchKernelGGL(bspline3d_prefilter_walk4_kernel<1>, dim3((dx + 255) / 256, (dz + 3) / 4, (dy + run - 1) / run), dim3(256), 0,
                            stream, (const float*)coef, tmp, dz, dy, dx, run);
-        (void)hipGetLastError();
+        if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
         hipLaunchKernelGGL(bspline3d_prefilter_walk4_kernel<0>, dim3((dx + 255) / 256, (dy + 3) / 4, (dz + run - 1) / run), dim3(256), 0,
                            stream, (const float*)tmp, coef, dz, dy, dx, run);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(bspline3d_prefilter_x_kernel, dim3((dx + 511) / 512, (dy + 3) / 4, dz), dim3(256), 0, stream, vol, coef, dz, dy, dx);
-    (void)hipGetLastError();
+    if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
     hipLaunchKernelGGL(bspline3d_prefilter_walk_kernel<1>, dim3((dx + 63) / 64, (dz + 3) / 4, (dy + run - 1) / run), dim3(256), 0,
                        stream, (const float*)coef, tmp, dz, dy, dx, run);
-    (void)hipGetLastError();
+    if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
     hipLaunchKernelGGL(bspline3d_prefilter_walk_kernel<0>, dim3((dx + 63) / 64, (dy + 3) / 4, (dz + run - 1) / run), dim3(256), 0,
                        stream, (const float*)tmp, coef, dz, dy, dx, run);
     return hipGetLastError();
