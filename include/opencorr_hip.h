@@ -85,7 +85,8 @@ typedef enum oc_hip_kind {
     OC_HIP_REGION_FIT = 10,
     OC_HIP_CALIBRATION = 11,
     OC_HIP_STEREOVISION = 12,
-    OC_HIP_MATCHER = 13
+    OC_HIP_MATCHER = 13,
+    OC_HIP_SIFT3D = 14
 } oc_hip_kind;
 
 #define OC_HIP_POI2D_BYTES 100
@@ -328,7 +329,7 @@ int oc_hip_group_queue(const oc_hip_engine* engine, int member, const void** dev
  * the key does not belong to, with OC_HIP_ERR_UNSUPPORTED.  The default of every key, its range, the engine kinds that may set
  * it and the values only the A/B build of the library accepts are stated ONCE, as a table: opencorr_amd/csrc/host/engine_tuning.h
  * (the initialisers of EngineTuning, the rows of kTuningKeys).  What the keys do:
- *   "arith_fma"       ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 only (and the descriptor matcher).  0: every
+ *   "arith_fma"       ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 only (and the descriptor matcher and the SIFT3D scale space, see there).  0: every
  *                     multiply and add of the solver rounds on its own -- the reference built for baseline x86-64; GPU ==
  *                     oracle OC_ORDER_LANES bit for bit.  1: every PER-SAMPLE multiply-add is one fused multiply-add -- what a
  *                     compiler with FMA hardware makes of the reference's source expressions (src/oc_cubic_bspline.cpp:159-177,
@@ -522,6 +523,48 @@ int oc_hip_matcher_nearest(oc_hip_engine* engine, int direction, int* matched_id
  * *n_pairs carries the needed size (min(count_ref, count_tar) always suffices).  The call waits for the stream. */
 int oc_hip_matcher_match(oc_hip_engine* engine, int mode, int* ref_idx, int* tar_idx, size_t capacity, size_t* n_pairs,
                          int memory);
+
+/* ---- SIFT3D's scale space: Gaussian / DoG pyramids and extrema ------------ */
+/* The front half of SIFT3D::compute(): createGaussianPyramid (src/oc_sift.cpp:676-754), createDogPyramid (:756-793) and
+ * detectExtrema (:795-847).  Volumes are [z][y][x], x contiguous, float32 (Image3D::vol_mat).  Arithmetic contract: the blur
+ * weights are the reference's (:371-399, computed on the host); every blurred voxel is acc = w[0] * s[c], then for
+ * r = 1 ... R in that order acc = acc + w[r] * (s[lo(c - r)] + s[hi(c + r)]) in float32 (fmaf(w[r], s_lo + s_hi, acc) under
+ * oc_hip_set_tuning("arith_fma", 1)), passes x, y, z; lo / hi are mirrorLow / mirrorHigh (:1505-1517).  One deviation, where the
+ * reference reads outside the array (axis radius > dim - 1): the reflected index is clamped into [0, dim - 1].  Non-finite
+ * voxels are outside the contract (they cannot affect addressing).  Supported: axis radii up to 32, up to 16 layers per octave,
+ * volumes up to 2^31-1 voxels; anything else is refused with OC_HIP_ERR_UNSUPPORTED before anything is launched.  The handle
+ * supports set_stream, synchronize, set_tuning ("arith_fma") and destroy; oc_hip_set_devices, oc_hip_compute* and
+ * oc_hip_set_images* are refused (OC_HIP_ERR_UNSUPPORTED).  Settings at creation: those of SIFT3D::SIFT3D() (:142-159). */
+typedef struct oc_hip_sift3d_candidate {
+    int x, y, z;      /* Keypoint3D::coor_layer (:833-835) */
+    int octave, layer; /* :836-837; layer = position of the DoG layer in its octave */
+    float scale;      /* the DoG layer's (:838) */
+} oc_hip_sift3d_candidate;
+int oc_hip_sift3d_create(int device, oc_hip_engine** out);
+/* the members of Sift3dConfig (src/oc_sift.h:71-83) the scale space reads; SIFT3D::setSiftConfig (:192-195) */
+int oc_hip_sift3d_set_config(oc_hip_engine* engine, int n_octave_layers, int min_dimension, float alpha, float sigma_source,
+                             float sigma_base);
+/* SIFT3D::setPhysicalUnit (:197-202) */
+int oc_hip_sift3d_set_physical_unit(oc_hip_engine* engine, float unit_x, float unit_y, float unit_z);
+/* The Image3D the pyramid is built from (:676).  OC_HIP_HOST volumes are copied; OC_HIP_DEVICE volumes are used in place and
+ * must stay valid until oc_hip_sift3d_build has returned. */
+int oc_hip_sift3d_set_volume(oc_hip_engine* engine, const float* data, int dim_x, int dim_y, int dim_z, int memory);
+/* createGaussianPyramid + createDogPyramid with max_abs of every DoG layer (:676-793).  Both pyramids stay on the device.
+ * The call waits for the stream. */
+int oc_hip_sift3d_build(oc_hip_engine* engine);
+/* pyramid 0 = Gaussian (n_octave * (n_octave_layers + 3) layers, :685-686), 1 = DoG (n_octave * (n_octave_layers + 2), :758-759) */
+int oc_hip_sift3d_layer_count(const oc_hip_engine* engine, int pyramid, int* n_layers, int* n_octave);
+/* The members of Layer3D (src/oc_sift.h:85-94) but vol_mat; every output may be null.  dims / units: { x, y, z }.  sigma: the
+ * value of :706 / :728 (0 for the bottom layer of an octave above the first and for DoG layers, which the reference leaves
+ * unset); max_abs: :777-787 for DoG layers, -1 for Gaussian ones. */
+int oc_hip_sift3d_layer_info(const oc_hip_engine* engine, int pyramid, int index, int* dims, float* units, int* octave,
+                             float* scale, float* sigma, float* max_abs);
+/* vol_mat of one layer as dims[2] * dims[1] * dims[0] floats where `memory` says */
+int oc_hip_sift3d_get_layer(oc_hip_engine* engine, int pyramid, int index, float* out, int memory);
+/* detectExtrema (:795-847): the candidates in the reference's scan order (octave, layer, z, y, x ascending), identical from
+ * run to run.  out: `capacity` records where `memory` says; *n (host, required) receives the number of candidates.  capacity
+ * smaller than that: OC_HIP_ERR_INVALID, nothing is written and *n carries the needed size.  The call waits for the stream. */
+int oc_hip_sift3d_detect(oc_hip_engine* engine, oc_hip_sift3d_candidate* out, size_t capacity, size_t* n, int memory);
 
 /* ---- introspection (tests, bench, profiling) ------------------------------ */
 int oc_hip_get_kind(const oc_hip_engine* engine, int* kind);

@@ -18,7 +18,7 @@ ERR_INVALID, ERR_HIP, ERR_ROCFFT, ERR_NOMEM, ERR_UNSUPPORTED = 1, 2, 3, 4, 5
 HOST, DEVICE = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 FFTCC2D, ICGN2D1, ICGN2D2, FFTCC3D, ICGN3D1, NR2D1, ICLM2D1, ICLM2D2, STRAIN, REGION_FIT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
-CALIBRATION, STEREOVISION, MATCHER = 11, 12, 13
+CALIBRATION, STEREOVISION, MATCHER, SIFT3D = 11, 12, 13, 14
 POI2D_BYTES, POI3D_BYTES, POI2DS_BYTES = 100, 124, 112
 POI2D_FLOATS, POI3D_FLOATS, POI2DS_FLOATS = 25, 31, 28
 POI2DS = 22  # the `ndim` of oc_hip_strain_prepare / oc_hip_strain_compute that selects POI2DS records
@@ -46,6 +46,8 @@ SYMBOLS = [
     "oc_hip_calibration_maps", "oc_hip_calibration_undistort",
     "oc_hip_stereo_create", "oc_hip_stereo_fundamental", "oc_hip_stereo_reconstruct", "oc_hip_stereo_reconstruct_pois",
     "oc_hip_matcher_create", "oc_hip_matcher_set_ratio", "oc_hip_matcher_set_descriptors", "oc_hip_matcher_nearest", "oc_hip_matcher_match",
+    "oc_hip_sift3d_create", "oc_hip_sift3d_set_config", "oc_hip_sift3d_set_physical_unit", "oc_hip_sift3d_set_volume", "oc_hip_sift3d_build",
+    "oc_hip_sift3d_layer_count", "oc_hip_sift3d_layer_info", "oc_hip_sift3d_get_layer", "oc_hip_sift3d_detect",
 ]
 
 
@@ -192,6 +194,15 @@ def lib():
     L.oc_hip_matcher_set_descriptors.argtypes = [vp, i, vp, sz, i]
     L.oc_hip_matcher_nearest.argtypes = [vp, i, vp, vp, vp, psz, i]
     L.oc_hip_matcher_match.argtypes = [vp, i, vp, vp, sz, psz, i]
+    L.oc_hip_sift3d_create.argtypes = [i, pp]
+    L.oc_hip_sift3d_set_config.argtypes = [vp, i, i, f, f, f]
+    L.oc_hip_sift3d_set_physical_unit.argtypes = [vp, f, f, f]
+    L.oc_hip_sift3d_set_volume.argtypes = [vp, vp, i, i, i, i]
+    L.oc_hip_sift3d_build.argtypes = [vp]
+    L.oc_hip_sift3d_layer_count.argtypes = [vp, i, vp, vp]
+    L.oc_hip_sift3d_layer_info.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp]
+    L.oc_hip_sift3d_get_layer.argtypes = [vp, i, i, vp, i]
+    L.oc_hip_sift3d_detect.argtypes = [vp, vp, sz, psz, i]
     for name in SYMBOLS:
         if name != "oc_hip_last_error":
             getattr(L, name).restype = i

@@ -695,6 +695,7 @@ int oc_hip_set_images2d(oc_hip_engine* e, const float* ref, const float* tar, in
                         int memory) {
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
+    if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: the SIFT3D scale space takes one volume (oc_hip_sift3d_set_volume)");
     if (e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images2d called on a 3D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null image pointer");
     if (height < 5 || width < 5) return fail(OC_HIP_ERR_INVALID, "image too small: %d x %d", width, height);
@@ -735,6 +736,7 @@ int oc_hip_set_images3d(oc_hip_engine* e, const float* ref, const float* tar, in
                         int memory) {
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
+    if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: the SIFT3D scale space takes one volume (oc_hip_sift3d_set_volume)");
     if (!e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images3d called on a 2D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null volume pointer");
     if (dim_x < 15 || dim_y < 15 || dim_z < 15)
@@ -823,6 +825,7 @@ int oc_hip_set_devices(oc_hip_engine* e, const int* device_ids, int n_devices) {
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Calibration / Stereovision handles stay on the device they were created for");
     if (n_devices > 1 && (e->kind == OC_HIP_STRAIN || e->kind == OC_HIP_REGION_FIT))
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Strain / RegionFit need every neighbour of a POI and stay on one device");
+    if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a SIFT3D scale space stays on the device it was created for");
     if (n_devices > 1 && e->is_matcher())
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a descriptor matcher needs every candidate of a query and stays on one device");
     int ndev = 0;
@@ -1088,6 +1091,7 @@ extern "C" {
 static int compute_impl(oc_hip_engine* e, void* pois, const float* offsets, size_t count, size_t stride_bytes, int memory) {
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
+    if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT3D scale space has no POI queue (oc_hip_sift3d_build / oc_hip_sift3d_detect)");
     if (count == 0) return OC_HIP_OK;
     if (!pois) return fail(OC_HIP_ERR_INVALID, "null POI buffer");
     if (stride_bytes < e->poi_bytes() || (stride_bytes & 3))
@@ -1136,6 +1140,8 @@ int oc_hip_compute_chain(oc_hip_engine* const* engines, int n_engines, void* poi
     for (int i = 0; i < n_engines; i++) OC_TRY(check_engine(engines[i]));
     for (int i = 0; i < n_engines; i++)
         if (engines[i]->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: a descriptor matcher has no POI queue");
+    for (int i = 0; i < n_engines; i++)
+        if (engines[i]->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: the SIFT3D scale space has no POI queue");
     if (n_engines == 1) return compute_impl(engines[0], pois, nullptr, count, stride_bytes, memory);
     oc_hip_engine* lead = engines[0];
     for (int i = 1; i < n_engines; i++) {
@@ -1259,6 +1265,7 @@ static void serve_single_batch(oc_hip_engine* e, std::vector<oc_hip_engine::Sing
 // per-POI solves are independent: tests/test_gpu_parity_2d.py::test_host_pipeline_chunks_change_no_bits).
 static int compute_single(oc_hip_engine* e, void* poi, const float* offset) {
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
+    if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT3D scale space has no POI queue (oc_hip_sift3d_build / oc_hip_sift3d_detect)");
     if (!poi) return fail(OC_HIP_ERR_INVALID, "null POI");
     if (!e->single_combine) return compute_impl(e, poi, offset, 1, e->poi_bytes(), OC_HIP_HOST);
     oc_hip_engine::SingleCombiner::Request req(poi, offset);

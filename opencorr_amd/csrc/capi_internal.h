@@ -54,6 +54,7 @@ ncclResult_t ncclGetVersion(int* version);
 #include "oc_kernels.h"
 #include "host/chunk_pipeline.h"
 #include "host/engine_tuning.h"
+#include "host/sift3d_plan.h"
 #include "host/single_combiner.h"
 
 namespace ochip_capi {
@@ -253,6 +254,15 @@ struct DeviceState {
     const float* mt_ext[2] = {nullptr, nullptr};
     DevBuf mt_desc[2], mt_idx[2], mt_best[2], mt_second[2];   // [direction] for the results: 0 = ref -> tar, 1 = tar -> ref
     DevBuf mt_part, mt_keys, mt_scan, mt_pairs, mt_counter;
+    // SIFT3D scale space (capi_sift3d.hip): the volume (a HOST volume is copied into sf_vol, a DEVICE one is used in place), both
+    // pyramids resident for the later stages, ONE scratch volume of octave-0 size (the y pass of every blur), the DoG maxima,
+    // the scan scratch and the staged list of oc_hip_sift3d_detect
+    const float* sf_ext = nullptr;
+    DevBuf sf_vol, sf_scratch, sf_max, sf_scan, sf_list;
+    std::vector<DevBuf> sf_gauss, sf_dog;
+    bool sf_built = false;
+    bool sf_counted = false;  // sf_scan holds the scanned per-workgroup counts of the pyramid as built, sf_total their sum
+    unsigned sf_total = 0;
     // FFTCC working set
     FftPlans fft;
     DevBuf win, freq, norms, flags;
@@ -295,6 +305,13 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
     // Descriptor matcher (capi_match.hip; SIFT3D::bruteforceMatch and the two match modes, src/oc_sift.cpp:625-674, 1251-1487)
     int mt_dim = 0;
     float mt_ratio = 0.f;
+    // SIFT3D scale space (capi_sift3d.hip; SIFT3D::createGaussianPyramid, createDogPyramid, detectExtrema, src/oc_sift.cpp:676-847):
+    // the settings, the volume's dims, the plan of the last build (host/sift3d_plan.h) and max_abs of every DoG layer
+    ochip_host::Sift3dSettings sf_cfg;
+    float sf_unit[3] = {1.f, 1.f, 1.f};
+    int sf_dim[3] = {0, 0, 0};
+    ochip_host::Sift3dPlan sf_plan;
+    std::vector<float> sf_max_abs;
     ochip_host::ChunkHandoff chunk_handoff;  // the copy-out thread sleeps here until the next chunk has been handed over
     std::atomic<unsigned> single_calls{0};  // compute(POI*) calls on this engine (one hint on stderr when a caller loops over them)
     // Combining front end of compute(POI*) (host/single_combiner.h): callers that arrive while a launch is in flight are queued;
@@ -320,6 +337,7 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
     mutable std::mutex mu;
 
     bool is_matcher() const { return kind == OC_HIP_MATCHER; }
+    bool is_sift3d() const { return kind == OC_HIP_SIFT3D; }
     bool is3d() const { return kind == OC_HIP_FFTCC3D || kind == OC_HIP_ICGN3D1; }
     bool is_iclm() const { return kind == OC_HIP_ICLM2D1 || kind == OC_HIP_ICLM2D2; }
     bool is_icgn2d() const { return kind == OC_HIP_ICGN2D1 || kind == OC_HIP_ICGN2D2 || is_iclm(); }

@@ -83,8 +83,8 @@ inline constexpr TuningKey kTuningKeys[] = {
     {"icgn2d_split_chunks", &EngineTuning::icgn2d_split_chunks, TuningRule::Range, 0, 256, "icgn2d_split_chunks must be 0 (back to back) ... 256",
      "icgn2d_split_chunks belongs to icgn2d_variant 8, an A/B partner" OC_AB_WORDS, kEveryKind, false, TuningAbOnly::NonZero},
     {"arith_fma", &EngineTuning::arith_fma, TuningRule::Bool, 0, 1, nullptr,
-     "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines and the descriptor matcher have a fused-arithmetic build",
-     kIcgn2dKinds | tuning_kind(OC_HIP_ICGN3D1) | tuning_kind(OC_HIP_MATCHER)},
+     "arith_fma: only the ICGN2D1 / ICGN2D2 / ICLM2D1 / ICLM2D2 / ICGN3D1 engines, the descriptor matcher and the SIFT3D scale space have a fused-arithmetic build",
+     kIcgn2dKinds | tuning_kind(OC_HIP_ICGN3D1) | tuning_kind(OC_HIP_MATCHER) | tuning_kind(OC_HIP_SIFT3D)},
     // (ICGN3D1 is refused in words of its own, OnePassOf3d: kTuningOnePassOf3dWords)
     {"arith_onepass", &EngineTuning::arith_onepass, TuningRule::Bool, 0, 1, nullptr, "arith_onepass: only the ICGN2D1 / ICGN2D2 engines have a one-pass build",
      tuning_kind(OC_HIP_ICGN2D1) | tuning_kind(OC_HIP_ICGN2D2)},

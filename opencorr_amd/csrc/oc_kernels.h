@@ -380,4 +380,42 @@ hipError_t launch_match_pairs_scatter(int mode, const int* r2t, const int* t2r, 
                                       size_t n_tar, float ratio_sq, const unsigned* scratch, int* ref_idx, int* tar_idx,
                                       hipStream_t stream);
 
+// ---- sift3d.hip -------------------------------------------------------------
+// SIFT3D's scale space (SIFT3D::gaussianBlur, downSampling, createDogPyramid, detectExtrema; src/oc_sift.cpp:365-562, 756-847).
+// Volumes are [z][y][x] float32, x contiguous.  Per blurred voxel: acc = w[0] * s[c], then r = 1 ... radius ascending
+// acc = acc + w[r] * (s[lo(c - r)] + s[hi(c + r)]) (fma: fmaf(w[r], s_lo + s_hi, acc)), the mirrored index clamped into the axis.
+constexpr int kSiftMaxRadius = 32;
+struct SiftWeights {
+    float w[kSiftMaxRadius + 1];
+};
+// the x pass: `rows` rows of nx floats
+hipError_t launch_sift_blur_x(const float* src, float* dst, int nx, size_t rows, const SiftWeights& w, int radius, bool fma, hipStream_t stream);
+// the y and z passes: the volume as [outer][n][inner], blurred along n (y: outer = nz, inner = nx; z: outer = 1, inner = ny * nx)
+hipError_t launch_sift_blur_strided(const float* src, float* dst, size_t outer, int n, size_t inner, const SiftWeights& w, int radius,
+                                    bool fma, hipStream_t stream);
+// dst[i][j][k] = src[2i][2j][2k]; src rows of sx floats, planes of sy rows
+hipError_t launch_sift_downsample(const float* src, int sx, int sy, float* dst, int dx, int dy, int dz, hipStream_t stream);
+// dog = g1 - g0 over `count` voxels; *max_abs_bits (set to 0 before) becomes the bit pattern of max fabsf(dog)
+hipError_t launch_sift_dog(const float* g0, const float* g1, float* dog, size_t count, unsigned* max_abs_bits, hipStream_t stream);
+// One DoG layer of the extrema search: a voxel with 1 <= index <= dim - 2 on every axis is a candidate when
+// fabsf(v) >= threshold and v is strictly greater, or strictly less, than its 6 face neighbours and the same voxel of the DoG
+// layers below and above.  A workgroup owns kSiftExtremaVoxels consecutive voxels; first_block: its workgroups' place among
+// those of all searched layers, in list order.
+constexpr int kSiftExtremaVoxels = 2048;
+struct SiftExtremaLayer {
+    const float *below, *here, *above;
+    int nx, ny, nz, octave, layer;
+    float scale, threshold;
+    unsigned first_block;
+};
+struct SiftCandidate {
+    int x, y, z, octave, layer;
+    float scale;
+};
+inline size_t sift_extrema_blocks(size_t voxels) { return (voxels + kSiftExtremaVoxels - 1) / kSiftExtremaVoxels; }
+// block_counts[2 * (first_block + b)] = candidates of workgroup b (the odd words 0): what launch_block_count_scan takes
+hipError_t launch_sift_extrema_count(const SiftExtremaLayer& layer, unsigned* block_counts, hipStream_t stream);
+// after the scan: the candidates at out[block_offsets[2 * block] + rank in scan order]
+hipError_t launch_sift_extrema_fill(const SiftExtremaLayer& layer, const unsigned* block_offsets, SiftCandidate* out, hipStream_t stream);
+
 }  // namespace ochip

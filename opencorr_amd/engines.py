@@ -800,6 +800,91 @@ class DescriptorMatcher(_Handle):
         return ref[:n.value], tar[:n.value]
 
 
+class SIFT3DScaleSpace(_Handle):
+    """SIFT3DScaleSpace() -- the front half of SIFT3D::compute (src/oc_sift.cpp:676-847): the Gaussian pyramid, the DoG pyramid
+    with ``max_abs`` per layer and the extrema candidates in the reference's scan order.  Volumes are (z, y, x) float32; a NumPy
+    volume is copied, a CUDA torch tensor is used in place by ``build``.  Both pyramids stay on the device; ``layer`` downloads
+    one (for a CPU ``assignOrientation``, say).  ``set_tuning("arith_fma", 1)``: fused multiply-adds in the blur sums."""
+
+    CANDIDATE = np.dtype([("x", np.int32), ("y", np.int32), ("z", np.int32), ("octave", np.int32), ("layer", np.int32), ("scale", np.float32)])
+    LAYER = np.dtype([("dims", np.int32, 3), ("units", np.float32, 3), ("octave", np.int32), ("scale", np.float32), ("sigma", np.float32),
+                      ("max_abs", np.float32)])
+    GAUSSIAN, DOG = 0, 1
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        self._volume = None
+        capi.check(capi.lib().oc_hip_sift3d_create(int(device), ctypes.byref(self._h)))
+
+    def set_tuning(self, key, value):
+        """``"arith_fma"`` (0 / 1)."""
+        capi.check(capi.lib().oc_hip_set_tuning(self._h, key.encode(), int(value)))
+
+    def set_config(self, n_octave_layers=3, min_dimension=8, alpha=0.1, sigma_source=1.15, sigma_base=1.6):
+        """The members of Sift3dConfig the scale space reads; the defaults are SIFT3D::SIFT3D()'s (src/oc_sift.cpp:142-159)."""
+        capi.check(capi.lib().oc_hip_sift3d_set_config(self._h, int(n_octave_layers), int(min_dimension), float(alpha), float(sigma_source),
+                                                       float(sigma_base)))
+
+    def set_physical_unit(self, unit_x, unit_y, unit_z):
+        capi.check(capi.lib().oc_hip_sift3d_set_physical_unit(self._h, float(unit_x), float(unit_y), float(unit_z)))
+
+    def set_volume(self, volume):
+        """``volume``: (dim_z, dim_y, dim_x) float32, a NumPy array or a CUDA torch tensor."""
+        if len(volume.shape) != 3:
+            raise ValueError("the volume must have shape (dim_z, dim_y, dim_x)")
+        self._adopt_stream_of(volume)
+        ptr, mem, keep = _buf(volume)
+        dz, dy, dx = (int(v) for v in volume.shape)
+        capi.check(capi.lib().oc_hip_sift3d_set_volume(self._h, ptr, dx, dy, dz, mem))
+        self._volume = keep if mem == capi.DEVICE else None   # a device volume is used in place: keep it alive
+
+    def build(self):
+        """createGaussianPyramid + createDogPyramid (src/oc_sift.cpp:676-793)."""
+        capi.check(capi.lib().oc_hip_sift3d_build(self._h))
+
+    def layers(self, pyramid):
+        """One ``LAYER`` record per layer of the Gaussian (0) or DoG (1) pyramid; dims and units are (x, y, z)."""
+        n, n_oct = ctypes.c_int(), ctypes.c_int()
+        capi.check(capi.lib().oc_hip_sift3d_layer_count(self._h, int(pyramid), ctypes.byref(n), ctypes.byref(n_oct)))
+        out = np.zeros(n.value, dtype=self.LAYER)
+        for i in range(n.value):
+            dims, units = (ctypes.c_int * 3)(), (ctypes.c_float * 3)()
+            octave, scale, sigma, max_abs = ctypes.c_int(), ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+            capi.check(capi.lib().oc_hip_sift3d_layer_info(self._h, int(pyramid), i, dims, units, ctypes.byref(octave), ctypes.byref(scale),
+                                                           ctypes.byref(sigma), ctypes.byref(max_abs)))
+            out[i] = (tuple(dims), tuple(units), octave.value, scale.value, sigma.value, max_abs.value)
+        return out
+
+    def layer(self, pyramid, index, out=None):
+        """The voxels of one layer as a (dim_z, dim_y, dim_x) float32 array; ``out``: a CUDA torch tensor of that shape to fill instead."""
+        dims = (ctypes.c_int * 3)()
+        capi.check(capi.lib().oc_hip_sift3d_layer_info(self._h, int(pyramid), int(index), dims, None, None, None, None, None))
+        shape = (dims[2], dims[1], dims[0])
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        elif tuple(out.shape) != shape:
+            raise ValueError("layer: the output must have shape %r" % (shape,))
+        if _is_torch(out):
+            ptr, mem, _ = _buf(out)
+        else:
+            if out.dtype != np.float32 or not out.flags.c_contiguous:
+                raise ValueError("layer: the output must be a contiguous float32 array")
+            ptr, mem = ctypes.c_void_p(out.ctypes.data), capi.HOST
+        capi.check(capi.lib().oc_hip_sift3d_get_layer(self._h, int(pyramid), int(index), ptr, mem))
+        return out
+
+    def detect(self):
+        """detectExtrema (src/oc_sift.cpp:795-847): a ``CANDIDATE`` array in the reference's scan order."""
+        n = ctypes.c_size_t()
+        rc = capi.lib().oc_hip_sift3d_detect(self._h, None, 0, ctypes.byref(n), capi.HOST)
+        if rc != capi.OK and n.value == 0:
+            capi.check(rc)
+        out = np.empty(n.value, dtype=self.CANDIDATE)
+        if n.value:
+            capi.check(capi.lib().oc_hip_sift3d_detect(self._h, ctypes.c_void_p(out.ctypes.data), n.value, ctypes.byref(n), capi.HOST))
+        return out
+
+
 class RegionFit:
     """RegionFit2D / RegionFit3D(neighbor_search_radius, neighbor_number_min, thread_number) -- src/oc_region_fit.h.
 
