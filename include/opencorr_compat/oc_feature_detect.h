@@ -1,23 +1,31 @@
-// oc_feature_detect.h -- the front half of the reference's SIFT3D::compute over the HIP C-ABI: createGaussianPyramid,
-// createDogPyramid and detectExtrema (src/oc_sift.cpp:676-754, 756-793, 795-847).
+// oc_feature_detect.h -- the reference's SIFT3D over the HIP C-ABI: createGaussianPyramid, createDogPyramid, detectExtrema,
+// assignOrientation and constructDescriptor (src/oc_sift.cpp:676-754, 756-793, 795-847, 849-1049, 1051-1249) and, with the
+// matcher of oc_feature_match.h, the whole of SIFT3D::compute (:234-293).
 //
 //   SIFT3DScaleSpace   setSiftConfig / setPhysicalUnit like SIFT3D's; compute(Image3D*) builds both pyramids on the device;
 //                      detectExtrema(kp_queue) appends the candidates exactly as :832-839 fills them (coor_layer, layer, octave,
-//                      scale; coor_img and rotation_matrix are the later stages'); downloadPyramid(pyramid, layers) hands the
-//                      layers to a CPU assignOrientation / constructDescriptor as Layer3D records with vol_mat[z][y][x].
+//                      scale); assignOrientation(kp_queue) replaces the queue by the accepted keypoints with coor_img and
+//                      rotation_matrix; constructDescriptor(kp_queue, descriptor) fills the reference's float** rows;
+//                      downloadPyramid(pyramid, layers) hands the layers out as Layer3D records with vol_mat[z][y][x].
+//   SIFT3D             the public interface of src/oc_sift.h:135-180 that a caller of compute() uses: setImages, prepare, compute,
+//                      clear, the config / unit / ratio setters and getters, ref_matched_kp, tar_matched_kp.  Keypoints and
+//                      descriptors never leave the device between the stages.
 //
-// One difference a caller can observe ("SIFT3D scale space"): where a blur radius exceeds dim - 1 on an axis the
-// reference's mirrored index leaves the array; here it is clamped into the axis.  Orientation, descriptors, SIFT2D and
-// FeatureAffine are not part of this header.
+// Differences a caller can observe ("SIFT3D scale space" and "SIFT3D orientation and descriptors"): where a blur
+// radius exceeds dim - 1 on an axis the reference's mirrored index leaves the array, here it is clamped into the axis; sums over
+// a keypoint's window are exact instead of sequential float32; the eigen-decomposition is a Jacobi iteration in double.  SIFT2D
+// and FeatureAffine are not part of this header.
 #pragma once
 
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../opencorr_hip.h"
 #include "oc_engines.h"
+#include "oc_feature_match.h"
 #include "oc_types.h"
 
 namespace opencorr {
@@ -117,6 +125,50 @@ public:
         }
     }
 
+    // assignOrientation (:849-1049): kp_queue becomes the accepted keypoints, in the queue's order, with coor_img and
+    // rotation_matrix set (:1020-1028, :1044-1045).  The queue must hold records of this pyramid (detectExtrema's).
+    void assignOrientation(std::vector<Keypoint3D>& kp_queue) {
+        feature_config();
+        std::vector<oc_hip_sift3d_candidate> list(kp_queue.size());
+        for (size_t i = 0; i < kp_queue.size(); i++) {
+            const Keypoint3D& kp = kp_queue[i];
+            if (kp.coor_layer.x != (float)(int)kp.coor_layer.x || kp.coor_layer.y != (float)(int)kp.coor_layer.y || kp.coor_layer.z != (float)(int)kp.coor_layer.z)
+                throw std::string("SIFT3DScaleSpace: keypoint coordinates must be whole voxels");
+            list[i] = oc_hip_sift3d_candidate{(int)kp.coor_layer.x, (int)kp.coor_layer.y, (int)kp.coor_layer.z, kp.octave, kp.layer, kp.scale};
+        }
+        std::vector<oc_hip_sift3d_keypoint> out(list.size());
+        size_t n = 0;
+        hipdetail::check(oc_hip_sift3d_orient(engine_, list.data(), list.size(), OC_HIP_HOST, out.data(), out.size(), &n, nullptr, nullptr, OC_HIP_HOST));
+        kp_queue.clear();
+        for (size_t i = 0; i < n; i++) kp_queue.push_back(from_record(out[i]));
+    }
+
+    // constructDescriptor (:1051-1249): descriptor[m][0 ... 767] for every keypoint of kp_queue (rows the caller allocated, new2D)
+    void constructDescriptor(std::vector<Keypoint3D>& kp_queue, float** descriptor) {
+        feature_config();
+        std::vector<oc_hip_sift3d_keypoint> list(kp_queue.size());
+        for (size_t i = 0; i < kp_queue.size(); i++) list[i] = to_record(kp_queue[i]);
+        std::vector<float> block(list.size() * 768);
+        hipdetail::check(oc_hip_sift3d_describe(engine_, list.data(), list.size(), OC_HIP_HOST, block.data(), OC_HIP_HOST));
+        for (size_t i = 0; i < list.size(); i++) std::memcpy(descriptor[i], block.data() + i * 768, 768 * sizeof(float));
+    }
+
+    // The two stages for every candidate of the pyramid, without a host list in between: the accepted keypoints (appended to
+    // kp_queue) and their descriptors as a device block [n][768] (null for n = 0) that lives until the next call or the end of this object.
+    const float* extractOnDevice(std::vector<Keypoint3D>& kp_queue) {
+        feature_config();
+        size_t n_candidates = 0, n = 0;
+        hipdetail::check(oc_hip_sift3d_candidate_count(engine_, &n_candidates));
+        std::vector<oc_hip_sift3d_keypoint> out(n_candidates);
+        hipdetail::check(oc_hip_sift3d_orient(engine_, nullptr, 0, OC_HIP_HOST, out.data(), out.size(), &n, nullptr, nullptr, OC_HIP_HOST));
+        for (size_t i = 0; i < n; i++) kp_queue.push_back(from_record(out[i]));
+        hipdetail::check(oc_hip_sift3d_describe(engine_, nullptr, n, OC_HIP_HOST, nullptr, OC_HIP_DEVICE));  // (the block stays in the engine)
+        const float* block = nullptr;
+        size_t count = 0;
+        if (n > 0) hipdetail::check(oc_hip_get_field(engine_, "descriptors", &block, &count));
+        return block;
+    }
+
     // pyramid 0 = Gaussian, 1 = DoG.  The records replace the contents of `layers`; their vol_mat stay valid until the next
     // download of the same pyramid or the end of this object.
     void downloadPyramid(int pyramid, std::vector<Layer3D>& layers) {
@@ -140,6 +192,31 @@ public:
     oc_hip_engine* handle() const { return engine_; }
 
 private:
+    void feature_config() {
+        hipdetail::check(oc_hip_sift3d_set_feature_config(engine_, sift_config.beta, sift_config.gamma, sift_config.gradient_threshold,
+                                                          sift_config.truncate_threshold));
+    }
+    static Keypoint3D from_record(const oc_hip_sift3d_keypoint& r) {
+        Keypoint3D kp{};
+        kp.coor_layer = Point3D(r.coor_layer[0], r.coor_layer[1], r.coor_layer[2]);
+        kp.coor_img = Point3D(r.coor_img[0], r.coor_img[1], r.coor_img[2]);
+        kp.octave = r.octave;
+        kp.layer = r.layer;
+        kp.scale = r.scale;
+        std::memcpy(kp.rotation_matrix, r.rotation_matrix, sizeof kp.rotation_matrix);
+        return kp;
+    }
+    static oc_hip_sift3d_keypoint to_record(const Keypoint3D& kp) {
+        oc_hip_sift3d_keypoint r{};
+        r.coor_layer[0] = kp.coor_layer.x, r.coor_layer[1] = kp.coor_layer.y, r.coor_layer[2] = kp.coor_layer.z;
+        r.coor_img[0] = kp.coor_img.x, r.coor_img[1] = kp.coor_img.y, r.coor_img[2] = kp.coor_img.z;
+        r.octave = kp.octave;
+        r.layer = kp.layer;
+        r.scale = kp.scale;
+        std::memcpy(r.rotation_matrix, kp.rotation_matrix, sizeof r.rotation_matrix);
+        return r;
+    }
+
     // one contiguous block with the reference's float*** view on it (new3D, src/oc_array.h)
     struct Volume {
         std::vector<float> data;
@@ -155,6 +232,67 @@ private:
     Sift3dConfig sift_config;
     float physical_unit[3] = {1.f, 1.f, 1.f};
     std::vector<std::unique_ptr<Volume>> store_[2];
+};
+
+// SIFT3D of the reference (src/oc_sift.h:135-180), for callers of compute(): two extractions and the matcher, descriptors handed
+// over as device blocks.  compute() ends with monodirectionalMatch like :285; setBidirectional(true) selects :288 instead.
+class SIFT3D {
+public:
+    std::vector<Point3D> ref_matched_kp;  // matched keypoints in ref image
+    std::vector<Point3D> tar_matched_kp;  // matched keypoints in tar image
+
+    SIFT3D() : matcher_(768, 0.85f) {}
+    SIFT3D(const SIFT3D&) = delete;
+    SIFT3D& operator=(const SIFT3D&) = delete;
+
+    void setImages(Image3D& ref_img, Image3D& tar_img) {  // Feature3D::setImages
+        this->ref_img = &ref_img;
+        this->tar_img = &tar_img;
+    }
+    Sift3dConfig getSiftConfig() const { return extractor_[0].getSiftConfig(); }
+    float getPhysicalUnit(int dim) const { return extractor_[0].getPhysicalUnit(dim); }
+    float getMatchingRatio() const { return matcher_.getMatchingRatio(); }
+    void setSiftConfig(Sift3dConfig sift_config) {
+        for (SIFT3DScaleSpace& s : extractor_) s.setSiftConfig(sift_config);
+    }
+    void setPhysicalUnit(float unit_x, float unit_y, float unit_z) {
+        for (SIFT3DScaleSpace& s : extractor_) s.setPhysicalUnit(unit_x, unit_y, unit_z);
+    }
+    void setMatchingRatio(float matching_ratio) { matcher_.setMatchingRatio(matching_ratio); }
+    void setBidirectional(bool on) { bidirectional_ = on; }
+
+    void prepare() {}  // (:209-232 fills the icosahedron: a constant of the descriptor kernel here)
+
+    void compute() {  // :234-293
+        if (!ref_img || !tar_img) throw std::string("SIFT3D: no images (setImages)");
+        std::vector<Keypoint3D> kp[2];
+        Image3D* img[2] = {ref_img, tar_img};
+        for (int side = 0; side < 2; side++) {
+            extractor_[side].compute(img[side]);
+            const float* block = extractor_[side].extractOnDevice(kp[side]);
+            matcher_.setDeviceDescriptors(side, block, (int)kp[side].size());
+        }
+        clear();
+        std::vector<Point3D> coor[2];
+        for (int side = 0; side < 2; side++)
+            for (const Keypoint3D& k : kp[side]) coor[side].push_back(k.coor_img);
+        if (bidirectional_) matcher_.bidirectionalMatch(coor[0], coor[1], ref_matched_kp, tar_matched_kp);
+        else matcher_.monodirectionalMatch(coor[0], coor[1], ref_matched_kp, tar_matched_kp);
+    }
+
+    void clear() {  // :295-299
+        std::vector<Point3D>().swap(ref_matched_kp);
+        std::vector<Point3D>().swap(tar_matched_kp);
+    }
+
+protected:
+    Image3D* ref_img = nullptr;
+    Image3D* tar_img = nullptr;
+
+private:
+    SIFT3DScaleSpace extractor_[2];  // one per image: each keeps its descriptor block alive until the match is done
+    DescriptorMatcher3D matcher_;
+    bool bidirectional_ = false;
 };
 
 }  // namespace opencorr

@@ -54,6 +54,15 @@ public:
         count_[side] = count;
     }
 
+    // a block that is already on the device (16-byte aligned; oc_hip_sift3d_describe writes such blocks): used in place, so it
+    // must stay valid until the side is set again
+    void setDeviceDescriptors(int side, const float* device_block, int count) {
+        if (side != 0 && side != 1) throw std::string("DescriptorMatcher3D: side must be 0 (reference) or 1 (target)");
+        if (count < 0) throw std::string("DescriptorMatcher3D: negative keypoint count");
+        hipdetail::check(oc_hip_matcher_set_descriptors(engine_, side, device_block, (size_t)count, OC_HIP_DEVICE));
+        count_[side] = count;
+    }
+
     // SIFT3D::bruteforceMatch (:625-674); direction 0: reference -> target (matched_idx has one entry per reference keypoint),
     // 1: target -> reference.  Returns the number of matches.
     int bruteforceMatch(int direction, int* matched_idx) {

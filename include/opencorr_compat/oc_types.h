@@ -46,6 +46,7 @@ public:
 inline Point3D operator+(Point3D a, Point3D b) { return Point3D(a.x + b.x, a.y + b.y, a.z + b.z); }
 inline Point3D operator-(Point3D a, Point3D b) { return Point3D(a.x - b.x, a.y - b.y, a.z - b.z); }
 inline Point3D operator*(float f, Point3D p) { return Point3D(f * p.x, f * p.y, f * p.z); }
+inline std::ostream& operator<<(std::ostream& output, const Point3D& point) { return output << point.x << "," << point.y << "," << point.z; }  // src/oc_point.h:148-152
 
 union DeformationVector2D {
     struct { float u, ux, uy, uxx, uxy, uyy, v, vx, vy, vxx, vxy, vyy; };

@@ -566,6 +566,73 @@ int oc_hip_sift3d_get_layer(oc_hip_engine* engine, int pyramid, int index, float
  * smaller than that: OC_HIP_ERR_INVALID, nothing is written and *n carries the needed size.  The call waits for the stream. */
 int oc_hip_sift3d_detect(oc_hip_engine* engine, oc_hip_sift3d_candidate* out, size_t capacity, size_t* n, int memory);
 
+/* ---- SIFT3D's orientation and descriptor stages --------------------------- */
+/* SIFT3D::assignOrientation (src/oc_sift.cpp:849-1049) and constructDescriptor (:1051-1249) on the pyramid of
+ * oc_hip_sift3d_build, on the same handle.  Arithmetic contract:
+ * 1. Per-voxel terms are the reference's float32 expressions in its order, each operation rounded on its own: the window bounds
+ *    as written (:863-876 -- :870 multiplies by unit_y where the other five bounds divide -- and :1066-1079), the IMG_BORDER
+ *    clamp, the sphere test norm <= radius, gradients (`0.5 * (a - b) / unit` as (0.5f * (a - b)) / unit: the same bits),
+ *    rotation, subregion coordinates, (int) truncation for the cube index against floor for the fraction (:1174-1187),
+ *    the 10 FLT_EPSILON magnitude test, cartisan2Barycentric (:579-623) over the 20 tiles of prepare() (:212-231) in ascending
+ *    order with the first hit winning, the trilinear weights and the three products per bin (:1209-1211).  Unqualified exp,
+ *    pow, sqrt, floor and fabs of float arguments are the float overloads.
+ * 2. Gaussian weights come from the host's libm, as tables over (|dx|, |dy|, |dz|) per layer: expf(-0.5f * (q * q)) with
+ *    q = norm / sigma_w in float (:902), (float)exp(-0.5 * (q * q)) with q = (double)(norm / sigma) (:1129); pow(q, 2) is q * q.
+ * 3. Sums over voxels are exact (the deliberate departure: the reference adds sequentially in float32 inside one thread).
+ *    With A = max |v| of the volume and E the smallest integer with 2^E >= 2 A / min(unit) (0 for A = 0), a term t becomes
+ *    the integer llrintf(ldexpf(t, -q)), q = E - 40 for the three d sums, 2 E - 40 for the six tensor sums, E - 39 for the
+ *    descriptor bins; the integers add up in 64 bits.  Back: int64 -> float32 with one rounding, times 2^q (d, the reported
+ *    sums, the bins); the tensor enters the eigen-decomposition as int64 -> double, times 2^q.  No result depends on the
+ *    order of the voxels, on the launch shape or on the run; a keypoint's bits depend on the rest of the volume through E only.
+ * 4. The eigen-decomposition (the reference calls Eigen::EigenSolver<Matrix3f>, :948) is a cyclic Jacobi iteration on the
+ *    symmetric 3 x 3 in double (pairs (0,1), (0,2), (1,2); t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)); a pair with
+ *    |a_pq| <= 2^-62 (|a_pp| + |a_qq|) is skipped; stop after a sweep without rotation or 16 sweeps).  Values and vectors
+ *    are rounded to float32; then :952-1048 follow as written.
+ * 5. Normalise / truncate / normalise (:1219-1247): the two 768-term sums are sequential float32 in ascending i.
+ * "arith_fma" keeps selecting how the Gaussian layers were blurred; these stages have one mode.
+ * Refused before any launch: OC_HIP_ERR_INVALID for a volume with non-finite voxels and for a record that names no layer
+ * keypoints lie in (octave in range, layer in 1 ... n_octave_layers), whose scale bits are not that layer's, whose coor_layer
+ * is not an integer inside the layer, or (keypoints) with a rotation entry that is not finite or beyond +-2 (no orthonormal
+ * matrix has one, and the grid has no room for it); OC_HIP_ERR_UNSUPPORTED for |E| > 60, a window of more than 2^20 voxels
+ * after clamping, a window half-extent above 80 voxels.  These three verdicts are the pyramid's: one layer beyond a limit refuses
+ * orient and describe for every record, also for records of layers that would fit.  Lists on the device are checked by a kernel
+ * that raises a flag.
+ * Cost on the entry points of the scale space: oc_hip_sift3d_build also finds A (one read of the volume and a 4-byte read-back),
+ * and oc_hip_sift3d_detect makes its list in the engine, where orient(candidates = NULL) reads it, and copies it out -- for an
+ * OC_HIP_DEVICE list that is one device-to-device copy and a second copy of the list (24 bytes per candidate) more than before. */
+typedef struct oc_hip_sift3d_keypoint {   /* Keypoint3D, src/oc_sift.h:96-103; 72 bytes */
+    float coor_layer[3];  /* x, y, z */
+    float coor_img[3];    /* coor_layer * 2^octave (:1044-1045) */
+    int octave, layer;
+    float scale;
+    float rotation_matrix[9];
+} oc_hip_sift3d_keypoint;
+/* The number of candidates of the pyramid as built -- what oc_hip_sift3d_detect reports in *n -- without a list buffer:
+ * the size of the status and sums arrays of oc_hip_sift3d_orient(candidates = NULL).  The count is made once per build. */
+int oc_hip_sift3d_candidate_count(oc_hip_engine* engine, size_t* n);
+/* beta, gamma, gradient_threshold, truncate_threshold of Sift3dConfig (src/oc_sift.h:71-83); at creation the values of
+ * SIFT3D::SIFT3D() (:147-152): 0.9, 0.4, 1e-10, 0.2 * 128 / 768.  Takes effect with the next orient / describe. */
+int oc_hip_sift3d_set_feature_config(oc_hip_engine* engine, float beta, float gamma, float gradient_threshold, float truncate_threshold);
+/* SIFT3D::assignOrientation (:849-1049).  candidates == NULL: the candidates of the pyramid as built, the list
+ * oc_hip_sift3d_detect returns, which is made on the device and stays there (n_candidates and candidates_memory are ignored;
+ * the count is oc_hip_sift3d_candidate_count's); otherwise n_candidates records where candidates_memory says.
+ * status (may be null, one int per candidate): 0 accepted, 1 gradient threshold (:930), 2 eigenvalues (:973-977), 3 angle
+ * (:1006).  sums (may be null, 9 floats per candidate): d_x d_y d_z, then the tensor xx xy xz yy yz zz.  out: the accepted
+ * keypoints in candidate order (:1039-1048), `capacity` records; out, status and sums live where `memory` says.  *n (host,
+ * required) receives the number of keypoints; capacity smaller than that: OC_HIP_ERR_INVALID, nothing is written and *n
+ * carries the needed size (n_candidates always suffices).  Either way the keypoints stay on the device for
+ * oc_hip_sift3d_describe(keypoints = NULL).  The call waits for the stream. */
+int oc_hip_sift3d_orient(oc_hip_engine* engine, const oc_hip_sift3d_candidate* candidates, size_t n_candidates, int candidates_memory,
+                         oc_hip_sift3d_keypoint* out, size_t capacity, size_t* n, int* status, float* sums, int memory);
+/* SIFT3D::constructDescriptor (:1051-1249).  keypoints == NULL: the output of the engine's last oc_hip_sift3d_orient (n must be
+ * its *n); otherwise n records where keypoints_memory says.  descriptors: n x 768 float32, row-major, where `memory` says -- an
+ * OC_HIP_DEVICE block (16-byte aligned) is directly usable by oc_hip_matcher_set_descriptors.  descriptors == NULL with
+ * OC_HIP_DEVICE: the block stays in the engine, oc_hip_get_field(engine, "descriptors", ...) hands it out, and it is valid
+ * until the next oc_hip_sift3d_describe on this handle or its destruction.  Process a long list in chunks: the descriptors of a
+ * million keypoints are 3 GB. */
+int oc_hip_sift3d_describe(oc_hip_engine* engine, const oc_hip_sift3d_keypoint* keypoints, size_t n, int keypoints_memory,
+                           float* descriptors, int memory);
+
 /* ---- introspection (tests, bench, profiling) ------------------------------ */
 int oc_hip_get_kind(const oc_hip_engine* engine, int* kind);
 /* Device pointers of the precomputed fields (row-major float32):
@@ -575,6 +642,7 @@ int oc_hip_get_kind(const oc_hip_engine* engine, int* kind);
  *                                                 src/oc_cubic_bspline.cpp:123-129, stored planar as [k][y][x][l]
  *                                                 (plane k = coef[k][0..3] of every pixel)  (3D: "coef", dz*dy*dx)
  *   "lut_gx","lut_gy"     4*height*width*4        NR2D1 after prepare: tables of the target gradients, same layout
+ *   "descriptors"         n*768                   SIFT3D after oc_hip_sift3d_describe(descriptors = NULL, OC_HIP_DEVICE)
  * Returns OC_HIP_ERR_INVALID for an unknown name or a field not built yet. */
 int oc_hip_get_field(const oc_hip_engine* engine, const char* name, const float** device_ptr, size_t* count);
 /* Copy a field to host memory (test helper). */

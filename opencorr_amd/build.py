@@ -20,14 +20,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libopencorr_hip.so")
-SOURCES = ["capi.hip", "capi_host.hip", "capi_group.hip", "capi_strain.hip", "capi_stereo.hip", "capi_match.hip", "match.hip", "capi_sift3d.hip", "sift3d.hip", "stereo.hip", "prepare2d.hip", "icgn2d.hip", "icgn2d_onepass.hip", "nr2d.hip", "poi_order.hip", "poi_split.hip", "strain.hip", "fftcc2d.hip", "fftcc2d_fused.hip", "fftcc2d_fusedn.hip", "fftcc2d_fusedp.hip", "fftcc2d_fusedr.hip", "fftcc2d_rect.hip", "prepare3d.hip", "icgn3d.hip", "icgn3d_onepass.hip", "fftcc3d.hip", "fftcc3d_fused.hip", "fftcc3d_fusedn.hip", "fftcc3d_box.hip", "fftcc3d_planes.hip", "fftcc3d_planesb.hip"]
+SOURCES = ["capi.hip", "capi_host.hip", "capi_group.hip", "capi_strain.hip", "capi_stereo.hip", "capi_match.hip", "match.hip", "capi_sift3d.hip", "sift3d.hip", "sift3d_features.hip", "stereo.hip", "prepare2d.hip", "icgn2d.hip", "icgn2d_onepass.hip", "nr2d.hip", "poi_order.hip", "poi_split.hip", "strain.hip", "fftcc2d.hip", "fftcc2d_fused.hip", "fftcc2d_fusedn.hip", "fftcc2d_fusedp.hip", "fftcc2d_fusedr.hip", "fftcc2d_rect.hip", "prepare3d.hip", "icgn3d.hip", "icgn3d_onepass.hip", "fftcc3d.hip", "fftcc3d_fused.hip", "fftcc3d_fusedn.hip", "fftcc3d_box.hip", "fftcc3d_planes.hip", "fftcc3d_planesb.hip"]
 # the A/B build: sources that exist only there, and the product sources whose code depends on OC_BUILD_AB (recompiled with
 # -DOC_BUILD_AB=1; every other object is shared with the product build)
 AB_ONLY_SOURCES = ["icgn3d_rows.hip", "icgn2d_band.hip", "fftcc3d_fused_r5.hip"]
 AB_DEPENDENT = ["capi.hip", "icgn2d.hip", "icgn3d.hip"]
 AB_LIBDIR = os.path.join(LIBDIR, "ab")
 AB_LIB = os.path.join(AB_LIBDIR, "libopencorr_hip_ab.so")
-HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "dic2d_device.h", "fft_device.h", "fftcc2d_fusedn_impl.h", "fftcc3d_planes_impl.h", "icgn3d_device.h", os.path.join("..", "..", "include", "opencorr_hip.h"),
+HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "sift3d_jacobi.h", "dic2d_device.h", "fft_device.h", "fftcc2d_fusedn_impl.h", "fftcc3d_planes_impl.h", "icgn3d_device.h", os.path.join("..", "..", "include", "opencorr_hip.h"),
            # host logic without HIP calls; in a subfolder, so that kernel_fingerprint()'s listing of csrc/ (no PMC record goes stale
            # from a host-only change) does not see them
            os.path.join("host", "single_combiner.h"), os.path.join("host", "chunk_pipeline.h"), os.path.join("host", "engine_tuning.h"),
@@ -35,7 +35,9 @@ HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "dic2d_device.h", "
            # instantiated, the lists of window sides of the second which FFTCC kernels
            os.path.join("host", "icgn2d_plan.h"), os.path.join("host", "fftcc_plan.h"),
            # the layer table and blur weights of the SIFT3D scale space (host arithmetic only)
-           os.path.join("host", "sift3d_plan.h")]
+           os.path.join("host", "sift3d_plan.h"),
+           # the weight tables, the grid of the exact sums and the refusals of its orientation and descriptor stages
+           os.path.join("host", "sift3d_feature_plan.h")]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP vectoriser pairs independent scalar fp32 operations into v_pk_mul_f32 / v_pk_add_f32.  On gfx950 a
 # packed op occupies a SIMD for 4.3 cycles against 2.4 for the plain one (profiles/r02b_valu_ubench.json) -- a 10 % gain that the
@@ -63,6 +65,8 @@ KERNEL_SOURCES = {
     "fftcc3d_fused32_kernel": ["fftcc3d_fused.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
     "match_top2_kernel": ["match.hip", "oc_device.h"],
     "sift_blur": ["sift3d.hip", "oc_device.h"],
+    "sift_orient_kernel": ["sift3d_features.hip", "sift3d_jacobi.h", "oc_device.h"],
+    "sift_describe_kernel": ["sift3d_features.hip", "sift3d_jacobi.h", "oc_device.h"],
     "fftcc3d_planes_kernel": ["fftcc3d_planes_impl.h", "fftcc3d_planes.hip", "fftcc3d_planesb.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
 }
 

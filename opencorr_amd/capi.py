@@ -48,6 +48,7 @@ SYMBOLS = [
     "oc_hip_matcher_create", "oc_hip_matcher_set_ratio", "oc_hip_matcher_set_descriptors", "oc_hip_matcher_nearest", "oc_hip_matcher_match",
     "oc_hip_sift3d_create", "oc_hip_sift3d_set_config", "oc_hip_sift3d_set_physical_unit", "oc_hip_sift3d_set_volume", "oc_hip_sift3d_build",
     "oc_hip_sift3d_layer_count", "oc_hip_sift3d_layer_info", "oc_hip_sift3d_get_layer", "oc_hip_sift3d_detect",
+    "oc_hip_sift3d_candidate_count", "oc_hip_sift3d_set_feature_config", "oc_hip_sift3d_orient", "oc_hip_sift3d_describe",
 ]
 
 
@@ -203,6 +204,10 @@ def lib():
     L.oc_hip_sift3d_layer_info.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp]
     L.oc_hip_sift3d_get_layer.argtypes = [vp, i, i, vp, i]
     L.oc_hip_sift3d_detect.argtypes = [vp, vp, sz, psz, i]
+    L.oc_hip_sift3d_candidate_count.argtypes = [vp, psz]
+    L.oc_hip_sift3d_set_feature_config.argtypes = [vp, f, f, f, f]
+    L.oc_hip_sift3d_orient.argtypes = [vp, vp, sz, i, vp, sz, psz, vp, vp, i]
+    L.oc_hip_sift3d_describe.argtypes = [vp, vp, sz, i, vp, i]
     for name in SYMBOLS:
         if name != "oc_hip_last_error":
             getattr(L, name).restype = i

@@ -1366,9 +1366,15 @@ int oc_hip_get_field(const oc_hip_engine* e, const char* name, const float** ptr
     if (!name || !ptr || !count) return fail(OC_HIP_ERR_INVALID, "null argument");
     *ptr = nullptr;
     *count = 0;
+    const std::string s(name);
+    if (e->is_sift3d()) {
+        if (s != "descriptors" || e->sf_desc_floats == 0) return fail(OC_HIP_ERR_INVALID, "get_field: '%s' is unknown or not built yet", name);
+        *ptr = e->sf_desc.as<float>();
+        *count = e->sf_desc_floats;
+        return OC_HIP_OK;
+    }
     if (!e->img) return fail(OC_HIP_ERR_INVALID, "get_field(%s): no images set", name);
     const size_t n = e->img->count();
-    const std::string s(name);
     if (s == "ref") { *ptr = e->img->ref_ptr(); *count = n; }
     else if (s == "tar") { *ptr = e->img->tar_ptr(); *count = n; }
     else if (s == "gx" && e->ref_ready) { *ptr = e->gx.as<float>(); *count = n; }

@@ -55,6 +55,7 @@ ncclResult_t ncclGetVersion(int* version);
 #include "host/chunk_pipeline.h"
 #include "host/engine_tuning.h"
 #include "host/sift3d_plan.h"
+#include "host/sift3d_feature_plan.h"
 #include "host/single_combiner.h"
 
 namespace ochip_capi {
@@ -263,6 +264,16 @@ struct DeviceState {
     bool sf_built = false;
     bool sf_counted = false;  // sf_scan holds the scanned per-workgroup counts of the pyramid as built, sf_total their sum
     unsigned sf_total = 0;
+    // ... and its orientation / descriptor stages: the weight tables and the layer records of the pyramid as built (sf_ftables,
+    // sf_flayers), max |v| of the volume, the per-candidate results of the last orient (status, nine sums, keypoint slots), its
+    // compacted output (sf_kp, what describe(NULL) reads), staged inputs and outputs of HOST calls
+    std::vector<DevBuf> sf_ftables;
+    DevBuf sf_flayers, sf_vmax, sf_status, sf_sums, sf_slots, sf_kp, sf_fscan, sf_flag, sf_in, sf_desc;
+    bool sf_listed = false;    // sf_list holds the list of the last detect (sf_total records)
+    bool sf_features = false;  // sf_ftables / sf_flayers belong to the pyramid as built
+    bool sf_oriented = false;  // sf_kp holds sf_kp_count keypoints of the pyramid as built
+    size_t sf_kp_count = 0;
+    size_t sf_desc_floats = 0;  // what the last describe(descriptors = NULL, OC_HIP_DEVICE) left in sf_desc ("descriptors" of oc_hip_get_field)
     // FFTCC working set
     FftPlans fft;
     DevBuf win, freq, norms, flags;
@@ -312,6 +323,11 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
     int sf_dim[3] = {0, 0, 0};
     ochip_host::Sift3dPlan sf_plan;
     std::vector<float> sf_max_abs;
+    // its orientation / descriptor stages (SIFT3D::assignOrientation, constructDescriptor, :849-1249): the settings, max |v| of
+    // the volume the pyramid was built from, the plan (host/sift3d_feature_plan.h)
+    ochip_host::Sift3dFeatureSettings sf_fcfg;
+    float sf_vol_max = 0.f;
+    ochip_host::Sift3dFeaturePlan sf_fplan;
     ochip_host::ChunkHandoff chunk_handoff;  // the copy-out thread sleeps here until the next chunk has been handed over
     std::atomic<unsigned> single_calls{0};  // compute(POI*) calls on this engine (one hint on stderr when a caller loops over them)
     // Combining front end of compute(POI*) (host/single_combiner.h): callers that arrive while a launch is in flight are queued;

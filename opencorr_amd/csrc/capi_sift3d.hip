@@ -1,10 +1,14 @@
 // capi_sift3d.hip -- SIFT3D's scale space (part of the C-ABI of include/opencorr_hip.h): SIFT3D::createGaussianPyramid,
-// createDogPyramid and detectExtrema of the reference (src/oc_sift.cpp:676-754, 756-793, 795-847) over the kernels of sift3d.hip.
-// The layer table, the blur weights and the support verdict come from host/sift3d_plan.h.  Everything runs on the engine's stream.
+// createDogPyramid and detectExtrema of the reference (src/oc_sift.cpp:676-754, 756-793, 795-847) over the kernels of sift3d.hip,
+// and its orientation and descriptor stages, assignOrientation and constructDescriptor (:849-1049, 1051-1249), over those of
+// sift3d_features.hip.  The layer table, the blur weights and the support verdict come from host/sift3d_plan.h; the Gaussian weight
+// tables, the grid of the exact sums and what is refused from host/sift3d_feature_plan.h.  Everything runs on the engine's stream.
 #include "capi_internal.h"
 
 static_assert(ochip::kSiftMaxRadius == ochip_host::kSift3dMaxRadius, "the plan admits what the kernels take");
 static_assert(sizeof(oc_hip_sift3d_candidate) == 24 && sizeof(ochip::SiftCandidate) == 24, "a candidate is 24 bytes");
+static_assert(sizeof(oc_hip_sift3d_keypoint) == 72 && sizeof(ochip::SiftKeypoint) == 72, "a keypoint is 72 bytes");
+static_assert(ochip::kSiftDescriptorLength == ochip_host::kSiftDescriptorLength, "one descriptor length");
 
 namespace {
 
@@ -67,6 +71,130 @@ std::vector<ochip::SiftExtremaLayer> extrema_layers(const oc_hip_engine* e, size
         }
     *total_blocks = blocks;
     return layers;
+}
+
+// The candidates of the pyramid as built: their number in sf_total (count and scan happen once per build: a caller that asks for
+// the size first and for the list next pays for them once) and, with `fill`, the list in sf_list, where it stays for
+// oc_hip_sift3d_orient(candidates = NULL).
+int candidate_list(oc_hip_engine* e, bool fill) {
+    size_t blocks = 0;
+    const std::vector<ochip::SiftExtremaLayer> layers = extrema_layers(e, &blocks);
+    if (layers.empty()) {
+        e->sf_total = 0;
+        e->sf_counted = e->sf_listed = true;  // (an empty list is a list)
+        return OC_HIP_OK;
+    }
+    OC_TRY(order_after_default_stream(e));
+    OC_TRY(e->sf_scan.reserve((2 * blocks + 2) * sizeof(unsigned)));
+    unsigned* counts = e->sf_scan.as<unsigned>();
+    unsigned* totals = counts + 2 * blocks;
+    if (!e->sf_counted) {
+        for (const ochip::SiftExtremaLayer& L : layers) OC_HIP_TRY(ochip::launch_sift_extrema_count(L, counts, e->stream));
+        OC_HIP_TRY(ochip::launch_block_count_scan(counts, blocks, totals, e->stream));
+        OC_HIP_TRY(hipMemcpyAsync(&e->sf_total, totals, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+        OC_HIP_TRY(hipStreamSynchronize(e->stream));
+        e->sf_counted = true;
+    }
+    if (!fill || e->sf_listed) return OC_HIP_OK;
+    if (e->sf_total > 0) {
+        OC_TRY(e->sf_list.reserve((size_t)e->sf_total * sizeof(ochip::SiftCandidate)));
+        for (const ochip::SiftExtremaLayer& L : layers)
+            OC_HIP_TRY(ochip::launch_sift_extrema_fill(L, counts, e->sf_list.as<ochip::SiftCandidate>(), e->stream));
+    }
+    e->sf_listed = true;
+    return OC_HIP_OK;
+}
+
+// The weight tables and the layer records of the pyramid as built, on the device; the verdict of host/sift3d_feature_plan.h
+// first: nothing is allocated or launched for a volume outside the supported range.
+int ensure_features(oc_hip_engine* e) {
+    if (e->sf_features) return OC_HIP_OK;
+    ochip_host::Sift3dFeaturePlan plan = ochip_host::sift3d_feature_plan(e->sf_plan, e->sf_vol_max);
+    if (plan.status != OC_HIP_OK) return fail(plan.status, "%s", plan.why.c_str());
+    const size_t n = e->sf_plan.gauss.size();
+    drain_engine(e);  // (a grow releases old blocks: nothing may still read them)
+    // the uploads below read `plan`'s vectors and `layers`: whichever way this function leaves, they have completed first
+    struct Settle {
+        oc_hip_engine* e;
+        ~Settle() {
+            (void)hipStreamSynchronize(e->stream);
+        }
+    } settle{e};
+    if (e->sf_ftables.size() < 2 * n) e->sf_ftables.resize(2 * n);
+    std::vector<ochip::SiftFeatureLayer> layers(n);
+    for (size_t i = 0; i < n; i++) {
+        const ochip_host::Sift3dLayer& g = e->sf_plan.gauss[i];
+        ochip::SiftFeatureLayer& L = layers[i];
+        L = ochip::SiftFeatureLayer{};
+        L.vol = e->sf_gauss[i].as<float>();
+        L.scale = g.scale;
+        for (int a = 0; a < 3; a++) {
+            L.dim[a] = g.dim[a];
+            L.unit[a] = g.unit[a];
+        }
+        const ochip_host::Sift3dFeatureTable* tables[2] = {&plan.orient[i], &plan.describe[i]};
+        for (int s = 0; s < 2; s++) {
+            const ochip_host::Sift3dFeatureTable& t = *tables[s];
+            if (t.weight.empty()) continue;
+            DevBuf& buf = e->sf_ftables[2 * i + (size_t)s];
+            OC_TRY(buf.reserve(t.weight.size() * sizeof(float)));
+            OC_HIP_TRY(hipMemcpyAsync(buf.p, t.weight.data(), t.weight.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+            (s == 0 ? L.orient : L.describe) = buf.as<float>();
+            for (int a = 0; a < 3; a++) (s == 0 ? L.orient_half : L.describe_half)[a] = t.half[a];
+        }
+        L.orient_radius = plan.orient[i].radius;
+        L.describe_radius = plan.describe[i].radius;
+        L.cube_radius = plan.describe[i].cube_radius;
+    }
+    OC_TRY(e->sf_flayers.reserve(n * sizeof(ochip::SiftFeatureLayer)));
+    OC_TRY(e->sf_flag.reserve(sizeof(unsigned)));
+    OC_HIP_TRY(hipMemcpyAsync(e->sf_flayers.p, layers.data(), n * sizeof(ochip::SiftFeatureLayer), hipMemcpyHostToDevice, e->stream));
+    OC_HIP_TRY(hipStreamSynchronize(e->stream));
+    e->sf_fplan = std::move(plan);
+    e->sf_features = true;
+    return OC_HIP_OK;
+}
+
+ochip::SiftFeatureParams feature_params(const oc_hip_engine* e) {
+    ochip::SiftFeatureParams p{};
+    p.layers = e->sf_flayers.as<ochip::SiftFeatureLayer>();
+    p.n_octave = e->sf_plan.n_octave;
+    p.n_octave_layers = e->sf_plan.n_octave_layers;
+    p.exponent = e->sf_fplan.exponent;
+    p.beta = e->sf_fcfg.beta;
+    p.gamma = e->sf_fcfg.gamma;
+    p.gradient_threshold = e->sf_fcfg.gradient_threshold;
+    p.truncate_threshold = e->sf_fcfg.truncate_threshold;
+    return p;
+}
+
+// a HOST list staged in sf_in, a DEVICE list in place
+template <class Record> int stage_list(oc_hip_engine* e, const char* what, const void* list, size_t n, int memory, const Record** d_list) {
+    if (memory == OC_HIP_DEVICE) {
+        if (reinterpret_cast<uintptr_t>(list) & 3) return fail(OC_HIP_ERR_INVALID, "%s: a device list must be 4-byte aligned", what);
+        *d_list = static_cast<const Record*>(list);
+        return OC_HIP_OK;
+    }
+    if (e->sf_in.bytes < n * sizeof(Record)) drain_engine(e);
+    OC_TRY(e->sf_in.reserve(n * sizeof(Record)));
+    OC_HIP_TRY(hipMemcpyAsync(e->sf_in.p, list, n * sizeof(Record), hipMemcpyHostToDevice, e->stream));
+    *d_list = e->sf_in.as<Record>();
+    return OC_HIP_OK;
+}
+
+// the records index the pyramid: a kernel reads the list where it lies and raises a flag, and nothing else is launched on a raised one
+template <class Record, class Launch>
+int check_list(oc_hip_engine* e, const char* what, const Record* d_list, size_t n, const ochip::SiftFeatureParams& p, Launch launch) {
+    unsigned flag = 0;
+    OC_HIP_TRY(hipMemsetAsync(e->sf_flag.p, 0, sizeof(unsigned), e->stream));
+    OC_HIP_TRY(launch(d_list, n, p, e->sf_flag.as<unsigned>(), e->stream));
+    OC_HIP_TRY(hipMemcpyAsync(&flag, e->sf_flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+    OC_HIP_TRY(hipStreamSynchronize(e->stream));
+    if (flag)
+        return fail(OC_HIP_ERR_INVALID,
+                    "%s: a record names no layer keypoints lie in (octave, layer 1 ... n_octave_layers), a scale that is not that layer's, a "
+                    "coordinate that is not an integer inside it, or a rotation entry that is not finite or beyond +-2", what);
+    return OC_HIP_OK;
 }
 
 }  // namespace
@@ -139,6 +267,7 @@ int oc_hip_sift3d_build(oc_hip_engine* e) {
     TailGuard tail(e);
     e->sf_built = false;
     e->sf_counted = false;
+    e->sf_listed = e->sf_features = e->sf_oriented = false;
     if (e->sf_dim[0] < 1) return fail(OC_HIP_ERR_INVALID, "sift3d_build: no volume (oc_hip_sift3d_set_volume)");
     // the verdict comes first: nothing is allocated or launched for a volume or a setting outside the supported range
     ochip_host::Sift3dPlan plan = ochip_host::sift3d_plan(e->sf_cfg, e->sf_dim[0], e->sf_dim[1], e->sf_dim[2], e->sf_unit[0], e->sf_unit[1], e->sf_unit[2]);
@@ -149,6 +278,7 @@ int oc_hip_sift3d_build(oc_hip_engine* e) {
     if (e->sf_dog.size() < n_dog) e->sf_dog.resize(n_dog);
     OC_TRY(e->sf_scratch.reserve(plan.gauss[0].voxels() * sizeof(float)));
     OC_TRY(e->sf_max.reserve(n_dog * sizeof(unsigned)));
+    OC_TRY(e->sf_vmax.reserve(sizeof(unsigned)));
     for (size_t i = 0; i < n_gauss; i++) OC_TRY(e->sf_gauss[i].reserve(plan.gauss[i].voxels() * sizeof(float)));
     for (size_t d = 0; d < n_dog; d++) OC_TRY(e->sf_dog[d].reserve(plan.gauss[(size_t)plan.dog_gauss((int)d)].voxels() * sizeof(float)));
     OC_TRY(order_after_default_stream(e));
@@ -170,9 +300,15 @@ int oc_hip_sift3d_build(oc_hip_engine* e) {
         OC_HIP_TRY(ochip::launch_sift_dog(e->sf_gauss[gi].as<float>(), e->sf_gauss[gi + 1].as<float>(), e->sf_dog[d].as<float>(), plan.gauss[gi].voxels(),
                                           e->sf_max.as<unsigned>() + d, e->stream));
     }
+    // max |v| of the volume: the grid of the exact sums of the orientation and descriptor stages (host/sift3d_feature_plan.h)
+    unsigned volume_bits = 0;
+    OC_HIP_TRY(hipMemsetAsync(e->sf_vmax.p, 0, sizeof(unsigned), e->stream));
+    OC_HIP_TRY(ochip::launch_sift_max_abs(volume, plan.gauss[0].voxels(), e->sf_vmax.as<unsigned>(), e->stream));
+    OC_HIP_TRY(hipMemcpyAsync(&volume_bits, e->sf_vmax.p, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
     std::vector<unsigned> bits(n_dog);
     OC_HIP_TRY(hipMemcpyAsync(bits.data(), e->sf_max.p, n_dog * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
     OC_HIP_TRY(hipStreamSynchronize(e->stream));
+    std::memcpy(&e->sf_vol_max, &volume_bits, sizeof(float));
     e->sf_max_abs.resize(n_dog);
     std::memcpy(e->sf_max_abs.data(), bits.data(), n_dog * sizeof(float));
     e->sf_plan = std::move(plan);
@@ -239,36 +375,158 @@ int oc_hip_sift3d_detect(oc_hip_engine* e, oc_hip_sift3d_candidate* out, size_t 
     std::lock_guard<std::mutex> lock(e->mu);
     TailGuard tail(e);
     OC_TRY(check_built(e, "sift3d_detect"));
-    size_t blocks = 0;
-    const std::vector<ochip::SiftExtremaLayer> layers = extrema_layers(e, &blocks);
-    if (layers.empty()) return OC_HIP_OK;
-    OC_TRY(order_after_default_stream(e));
-    OC_TRY(e->sf_scan.reserve((2 * blocks + 2) * sizeof(unsigned)));
-    unsigned* counts = e->sf_scan.as<unsigned>();
-    unsigned* totals = counts + 2 * blocks;
-    // (a caller that asks for the size first and for the list next pays for the count and the scan once: they belong to the
-    // pyramid as built, and every build starts over)
-    if (!e->sf_counted) {
-        for (const ochip::SiftExtremaLayer& L : layers) OC_HIP_TRY(ochip::launch_sift_extrema_count(L, counts, e->stream));
-        OC_HIP_TRY(ochip::launch_block_count_scan(counts, blocks, totals, e->stream));
-        OC_HIP_TRY(hipMemcpyAsync(&e->sf_total, totals, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
-        OC_HIP_TRY(hipStreamSynchronize(e->stream));
-        e->sf_counted = true;
-    }
+    OC_TRY(candidate_list(e, false));
     const unsigned total = e->sf_total;
     *n = total;
     if (total > capacity)
         return fail(OC_HIP_ERR_INVALID, "sift3d_detect: %u candidates do not fit the capacity of %zu (n carries the needed size)", total, capacity);
     if (total == 0) return OC_HIP_OK;
-    ochip::SiftCandidate* d_out = reinterpret_cast<ochip::SiftCandidate*>(out);
-    if (memory == OC_HIP_HOST) {
-        OC_TRY(e->sf_list.reserve((size_t)total * sizeof(ochip::SiftCandidate)));
-        d_out = e->sf_list.as<ochip::SiftCandidate>();
-    }
-    for (const ochip::SiftExtremaLayer& L : layers) OC_HIP_TRY(ochip::launch_sift_extrema_fill(L, counts, d_out, e->stream));
-    if (memory == OC_HIP_HOST) OC_HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)total * sizeof(ochip::SiftCandidate), hipMemcpyDeviceToHost, e->stream));
+    OC_TRY(candidate_list(e, true));
+    OC_HIP_TRY(hipMemcpyAsync(out, e->sf_list.p, (size_t)total * sizeof(ochip::SiftCandidate),
+                              memory == OC_HIP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
     OC_HIP_TRY(hipStreamSynchronize(e->stream));
     return OC_HIP_OK;
+}
+
+int oc_hip_sift3d_candidate_count(oc_hip_engine* e, size_t* n) {
+    OC_TRY(check_sift3d(e, "sift3d_candidate_count"));
+    OC_ACTIVATE(e);
+    if (!n) return fail(OC_HIP_ERR_INVALID, "sift3d_candidate_count: null n");
+    *n = 0;
+    std::lock_guard<std::mutex> lock(e->mu);
+    TailGuard tail(e);
+    OC_TRY(check_built(e, "sift3d_candidate_count"));
+    OC_TRY(candidate_list(e, false));
+    *n = e->sf_total;
+    return OC_HIP_OK;
+}
+
+int oc_hip_sift3d_set_feature_config(oc_hip_engine* e, float beta, float gamma, float gradient_threshold, float truncate_threshold) {
+    OC_TRY(check_sift3d(e, "sift3d_set_feature_config"));
+    if (!std::isfinite(beta) || !std::isfinite(gamma) || !std::isfinite(gradient_threshold) || !std::isfinite(truncate_threshold))
+        return fail(OC_HIP_ERR_INVALID, "sift3d_set_feature_config: beta, gamma, gradient_threshold and truncate_threshold must be finite");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->sf_fcfg.beta = beta;
+    e->sf_fcfg.gamma = gamma;
+    e->sf_fcfg.gradient_threshold = gradient_threshold;
+    e->sf_fcfg.truncate_threshold = truncate_threshold;
+    return OC_HIP_OK;
+}
+
+int oc_hip_sift3d_orient(oc_hip_engine* e, const oc_hip_sift3d_candidate* candidates, size_t n_candidates, int candidates_memory,
+                         oc_hip_sift3d_keypoint* out, size_t capacity, size_t* n, int* status, float* sums, int memory) {
+    OC_TRY(check_sift3d(e, "sift3d_orient"));
+    OC_ACTIVATE(e);
+    if (memory != OC_HIP_HOST && memory != OC_HIP_DEVICE) return fail(OC_HIP_ERR_INVALID, "sift3d_orient: bad memory kind %d", memory);
+    if (candidates && candidates_memory != OC_HIP_HOST && candidates_memory != OC_HIP_DEVICE)
+        return fail(OC_HIP_ERR_INVALID, "sift3d_orient: bad memory kind %d of the candidates", candidates_memory);
+    if (!n) return fail(OC_HIP_ERR_INVALID, "sift3d_orient: null n");
+    *n = 0;
+    if (capacity > 0 && !out) return fail(OC_HIP_ERR_INVALID, "sift3d_orient: null output buffer");
+    if (memory == OC_HIP_DEVICE && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(status) | reinterpret_cast<uintptr_t>(sums)) & 3))
+        return fail(OC_HIP_ERR_INVALID, "sift3d_orient: device outputs must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TailGuard tail(e);
+    OC_TRY(check_built(e, "sift3d_orient"));
+    if (!candidates) {
+        OC_TRY(candidate_list(e, true));
+        n_candidates = e->sf_total;
+    }
+    if (n_candidates > 0x7fffffffull) return fail(OC_HIP_ERR_UNSUPPORTED, "sift3d_orient: at most 2^31-1 candidates per call");
+    e->sf_oriented = false;
+    if (n_candidates == 0) {
+        e->sf_kp_count = 0;
+        e->sf_oriented = true;
+        return OC_HIP_OK;
+    }
+    OC_TRY(ensure_features(e));
+    OC_TRY(order_after_default_stream(e));
+    const ochip::SiftCandidate* d_list = e->sf_list.as<ochip::SiftCandidate>();
+    if (candidates) OC_TRY(stage_list<ochip::SiftCandidate>(e, "sift3d_orient", candidates, n_candidates, candidates_memory, &d_list));
+    const ochip::SiftFeatureParams p = feature_params(e);
+    OC_TRY(check_list(e, "sift3d_orient", d_list, n_candidates, p, ochip::launch_sift_check_candidates));
+    const size_t blocks = ochip::sift_orient_blocks(n_candidates);
+    drain_engine(e);  // (a grow releases old blocks: nothing may still read them)
+    OC_TRY(e->sf_status.reserve(n_candidates * sizeof(int)));
+    OC_TRY(e->sf_sums.reserve(n_candidates * 9 * sizeof(float)));
+    OC_TRY(e->sf_slots.reserve(n_candidates * sizeof(ochip::SiftKeypoint)));
+    OC_TRY(e->sf_fscan.reserve((2 * blocks + 2) * sizeof(unsigned)));
+    int* d_status = e->sf_status.as<int>();
+    unsigned* counts = e->sf_fscan.as<unsigned>();
+    unsigned* totals = counts + 2 * blocks;
+    {
+        ProfScope prof(e);
+        OC_HIP_TRY(ochip::launch_sift_orient(d_list, n_candidates, p, d_status, e->sf_sums.as<float>(), e->sf_slots.as<ochip::SiftKeypoint>(), e->stream));
+    }
+    OC_HIP_TRY(ochip::launch_sift_orient_count(d_status, n_candidates, counts, e->stream));
+    OC_HIP_TRY(ochip::launch_block_count_scan(counts, blocks, totals, e->stream));
+    unsigned total = 0;
+    OC_HIP_TRY(hipMemcpyAsync(&total, totals, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+    OC_HIP_TRY(hipStreamSynchronize(e->stream));
+    OC_TRY(e->sf_kp.reserve((size_t)total * sizeof(ochip::SiftKeypoint)));
+    if (total > 0)
+        OC_HIP_TRY(ochip::launch_sift_orient_fill(d_status, e->sf_slots.as<ochip::SiftKeypoint>(), n_candidates, counts, e->sf_kp.as<ochip::SiftKeypoint>(),
+                                                  e->stream));
+    e->sf_kp_count = total;
+    e->sf_oriented = true;
+    *n = total;
+    if (total > capacity) {
+        OC_HIP_TRY(hipStreamSynchronize(e->stream));
+        return fail(OC_HIP_ERR_INVALID, "sift3d_orient: %u keypoints do not fit the capacity of %zu (n carries the needed size)", total, capacity);
+    }
+    const hipMemcpyKind kind = memory == OC_HIP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (total > 0) OC_HIP_TRY(hipMemcpyAsync(out, e->sf_kp.p, (size_t)total * sizeof(ochip::SiftKeypoint), kind, e->stream));
+    if (status) OC_HIP_TRY(hipMemcpyAsync(status, d_status, n_candidates * sizeof(int), kind, e->stream));
+    if (sums) OC_HIP_TRY(hipMemcpyAsync(sums, e->sf_sums.p, n_candidates * 9 * sizeof(float), kind, e->stream));
+    OC_HIP_TRY(hipStreamSynchronize(e->stream));
+    return OC_HIP_OK;
+}
+
+int oc_hip_sift3d_describe(oc_hip_engine* e, const oc_hip_sift3d_keypoint* keypoints, size_t n, int keypoints_memory, float* descriptors, int memory) {
+    OC_TRY(check_sift3d(e, "sift3d_describe"));
+    OC_ACTIVATE(e);
+    if (memory != OC_HIP_HOST && memory != OC_HIP_DEVICE) return fail(OC_HIP_ERR_INVALID, "sift3d_describe: bad memory kind %d", memory);
+    if (keypoints && keypoints_memory != OC_HIP_HOST && keypoints_memory != OC_HIP_DEVICE)
+        return fail(OC_HIP_ERR_INVALID, "sift3d_describe: bad memory kind %d of the keypoints", keypoints_memory);
+    if (memory == OC_HIP_DEVICE && (reinterpret_cast<uintptr_t>(descriptors) & 3))
+        return fail(OC_HIP_ERR_INVALID, "sift3d_describe: a device block must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TailGuard tail(e);
+    OC_TRY(check_built(e, "sift3d_describe"));
+    if (!keypoints) {
+        if (!e->sf_oriented) return fail(OC_HIP_ERR_INVALID, "sift3d_describe: no keypoints on the device yet (oc_hip_sift3d_orient)");
+        if (n != e->sf_kp_count) return fail(OC_HIP_ERR_INVALID, "sift3d_describe: the last orient left %zu keypoints, not %zu", e->sf_kp_count, n);
+    }
+    if (n > 0x7fffffffull) return fail(OC_HIP_ERR_UNSUPPORTED, "sift3d_describe: at most 2^31-1 keypoints per call");
+    const bool keep = !descriptors && memory == OC_HIP_DEVICE;  // the block stays in the engine ("descriptors" of oc_hip_get_field)
+    if (keep) e->sf_desc_floats = 0;
+    if (n == 0) return OC_HIP_OK;
+    if (!descriptors && !keep) return fail(OC_HIP_ERR_INVALID, "sift3d_describe: null output buffer");
+    OC_TRY(ensure_features(e));
+    OC_TRY(order_after_default_stream(e));
+    const ochip::SiftKeypoint* d_list = e->sf_kp.as<ochip::SiftKeypoint>();
+    if (keypoints) OC_TRY(stage_list<ochip::SiftKeypoint>(e, "sift3d_describe", keypoints, n, keypoints_memory, &d_list));
+    const ochip::SiftFeatureParams p = feature_params(e);
+    OC_TRY(check_list(e, "sift3d_describe", d_list, n, p, ochip::launch_sift_check_keypoints));
+    float* d_out = descriptors;
+    const size_t bytes = n * ochip::kSiftDescriptorLength * sizeof(float);
+    if (memory == OC_HIP_HOST || keep) {
+        e->sf_desc_floats = 0;  // (a HOST call stages in the same block)
+        if (e->sf_desc.bytes < bytes) drain_engine(e);
+        OC_TRY(e->sf_desc.reserve(bytes));
+        d_out = e->sf_desc.as<float>();
+    }
+    {
+        ProfScope prof(e);
+        OC_HIP_TRY(ochip::launch_sift_describe(d_list, n, p, d_out, e->stream));
+    }
+    if (memory == OC_HIP_HOST) {
+        OC_HIP_TRY(hipMemcpyAsync(descriptors, d_out, bytes, hipMemcpyDeviceToHost, e->stream));
+        OC_HIP_TRY(hipStreamSynchronize(e->stream));
+        return OC_HIP_OK;
+    }
+    if (keep) e->sf_desc_floats = n * ochip::kSiftDescriptorLength;
+    return finish_device_call(e);
 }
 
 }  // extern "C"

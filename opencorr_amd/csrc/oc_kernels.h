@@ -418,4 +418,47 @@ hipError_t launch_sift_extrema_count(const SiftExtremaLayer& layer, unsigned* bl
 // after the scan: the candidates at out[block_offsets[2 * block] + rank in scan order]
 hipError_t launch_sift_extrema_fill(const SiftExtremaLayer& layer, const unsigned* block_offsets, SiftCandidate* out, hipStream_t stream);
 
+// ---- sift3d_features.hip ----------------------------------------------------
+// SIFT3D's orientation and descriptor stages (SIFT3D::assignOrientation, constructDescriptor; src/oc_sift.cpp:849-1049, 1051-1249).
+// Per-voxel terms are the reference's float32 expressions; the Gaussian weights come from the tables of
+// host/sift3d_feature_plan.h; sums over voxels are 64-bit integers on the grid that header defines.
+struct SiftFeatureLayer {   // one Gaussian layer; orient / describe: its weight tables ([|dz|][|dy|][|dx|], half-extents *_half)
+    const float* vol;
+    const float* orient;
+    const float* describe;
+    int dim[3], orient_half[3], describe_half[3];
+    float unit[3];
+    float scale, orient_radius, describe_radius, cube_radius;   // window_radius (:860), sphere_radius (:1062), cube_radius (:1063)
+};
+struct SiftFeatureParams {
+    const SiftFeatureLayer* layers;   // device, n_octave * (n_octave_layers + 3)
+    int n_octave, n_octave_layers;
+    int exponent;                     // E of the grid
+    float beta, gamma, gradient_threshold, truncate_threshold;
+};
+struct SiftKeypoint {   // oc_hip_sift3d_keypoint
+    float coor_layer[3], coor_img[3];
+    int octave, layer;
+    float scale;
+    float rotation_matrix[9];
+};
+constexpr int kSiftDescriptorLength = 768;
+// *max_abs_bits (set to 0 before) becomes the bit pattern of max fabsf(v); a NaN or an infinity gives a pattern >= 0x7f800000
+hipError_t launch_sift_max_abs(const float* v, size_t count, unsigned* max_abs_bits, hipStream_t stream);
+// *flag (set to 0 before) is raised when a record names no layer a keypoint can lie in, a scale that is not that layer's, or a
+// coordinate outside it (keypoints: also a non-integer or non-finite coordinate, a rotation entry that is not finite or beyond +-2)
+hipError_t launch_sift_check_candidates(const SiftCandidate* list, size_t n, const SiftFeatureParams& p, unsigned* flag, hipStream_t stream);
+hipError_t launch_sift_check_keypoints(const SiftKeypoint* list, size_t n, const SiftFeatureParams& p, unsigned* flag, hipStream_t stream);
+// assignOrientation for n validated candidates: status[i] (0 accepted, 1 gradient threshold, 2 eigenvalues, 3 angle), sums[9 i ...]
+// (d_x d_y d_z, tensor xx xy xz yy yz zz) and the keypoint record of candidate i at slots[i] (the rotation matrix only when accepted)
+hipError_t launch_sift_orient(const SiftCandidate* list, size_t n, const SiftFeatureParams& p, int* status, float* sums, SiftKeypoint* slots,
+                              hipStream_t stream);
+// the accepted slots in candidate order: count -> launch_block_count_scan -> fill (block_counts: 2 words per 256 candidates)
+inline size_t sift_orient_blocks(size_t n) { return (n + 255) / 256; }
+hipError_t launch_sift_orient_count(const int* status, size_t n, unsigned* block_counts, hipStream_t stream);
+hipError_t launch_sift_orient_fill(const int* status, const SiftKeypoint* slots, size_t n, const unsigned* block_offsets, SiftKeypoint* out,
+                                   hipStream_t stream);
+// constructDescriptor for n validated keypoints: out[768 i ...]
+hipError_t launch_sift_describe(const SiftKeypoint* list, size_t n, const SiftFeatureParams& p, float* out, hipStream_t stream);
+
 }  // namespace ochip

@@ -801,19 +801,25 @@ class DescriptorMatcher(_Handle):
 
 
 class SIFT3DScaleSpace(_Handle):
-    """SIFT3DScaleSpace() -- the front half of SIFT3D::compute (src/oc_sift.cpp:676-847): the Gaussian pyramid, the DoG pyramid
-    with ``max_abs`` per layer and the extrema candidates in the reference's scan order.  Volumes are (z, y, x) float32; a NumPy
+    """SIFT3DScaleSpace() -- the extraction half of SIFT3D::compute (src/oc_sift.cpp:676-1249): the Gaussian pyramid, the DoG
+    pyramid with ``max_abs`` per layer, the extrema candidates in the reference's scan order (``detect``), their orientation
+    (``orient``) and the 768-float descriptors of the accepted keypoints (``describe``).  Volumes are (z, y, x) float32; a NumPy
     volume is copied, a CUDA torch tensor is used in place by ``build``.  Both pyramids stay on the device; ``layer`` downloads
-    one (for a CPU ``assignOrientation``, say).  ``set_tuning("arith_fma", 1)``: fused multiply-adds in the blur sums."""
+    one.  ``set_tuning("arith_fma", 1)``: fused multiply-adds in the blur sums (the later stages have one arithmetic mode)."""
 
     CANDIDATE = np.dtype([("x", np.int32), ("y", np.int32), ("z", np.int32), ("octave", np.int32), ("layer", np.int32), ("scale", np.float32)])
     LAYER = np.dtype([("dims", np.int32, 3), ("units", np.float32, 3), ("octave", np.int32), ("scale", np.float32), ("sigma", np.float32),
                       ("max_abs", np.float32)])
+    KEYPOINT = np.dtype([("coor_layer", np.float32, 3), ("coor_img", np.float32, 3), ("octave", np.int32), ("layer", np.int32), ("scale", np.float32),
+                         ("rotation_matrix", np.float32, 9)])
     GAUSSIAN, DOG = 0, 1
+    ACCEPTED, REJECT_GRADIENT, REJECT_EIGENVALUES, REJECT_ANGLE = 0, 1, 2, 3
+    DESCRIPTOR_LENGTH = 768
 
     def __init__(self, device=0):
         super().__init__(device)
         self._volume = None
+        self._kp_count = 0
         capi.check(capi.lib().oc_hip_sift3d_create(int(device), ctypes.byref(self._h)))
 
     def set_tuning(self, key, value):
@@ -883,6 +889,138 @@ class SIFT3DScaleSpace(_Handle):
         if n.value:
             capi.check(capi.lib().oc_hip_sift3d_detect(self._h, ctypes.c_void_p(out.ctypes.data), n.value, ctypes.byref(n), capi.HOST))
         return out
+
+    def set_feature_config(self, beta=0.9, gamma=0.4, gradient_threshold=0.0000000001, truncate_threshold=float(np.float32(0.2) * 128 / 768)):
+        """The members of Sift3dConfig ``orient`` and ``describe`` read; the defaults are SIFT3D::SIFT3D()'s (src/oc_sift.cpp:147-152)."""
+        capi.check(capi.lib().oc_hip_sift3d_set_feature_config(self._h, float(beta), float(gamma), float(gradient_threshold), float(truncate_threshold)))
+
+    @staticmethod
+    def _records(x, dtype, what):
+        """(pointer, count, memory kind, keep-alive) of a structured NumPy array of ``dtype`` or a CUDA int32 tensor (n, words)"""
+        words = dtype.itemsize // 4
+        if _is_torch(x):
+            import torch
+            if x.dtype != torch.int32 or x.dim() != 2 or x.shape[1] != words or not x.is_cuda or not x.is_contiguous():
+                raise ValueError("%s: need a contiguous CUDA int32 tensor of shape (n, %d) (the records' 32-bit words)" % (what, words))
+            return ctypes.c_void_p(x.data_ptr()), int(x.shape[0]), capi.DEVICE, x
+        a = np.ascontiguousarray(x, dtype=dtype)
+        if a.ndim != 1:
+            raise ValueError("%s: need a one-dimensional array of records" % what)
+        return ctypes.c_void_p(a.ctypes.data), len(a), capi.HOST, a
+
+    def orient(self, candidates=None, with_status=False, on_device=False):
+        """assignOrientation (src/oc_sift.cpp:849-1049): the accepted keypoints in candidate order.  ``candidates``: None = the candidates
+        of the pyramid as built (what ``detect`` returns), which never leave the device; a ``CANDIDATE`` array; or a CUDA int32 tensor (n, 6) of the same records.
+        Results are NumPy (a ``KEYPOINT`` array) unless ``on_device`` or a tensor went in: then a CUDA int32 tensor (n, 18) of the
+        records' words.  ``with_status``: also ``status`` (one int per candidate: 0 accepted, 1 gradient threshold, 2 eigenvalues,
+        3 angle) and ``sums`` (n, 9: d_x d_y d_z, tensor xx xy xz yy yz zz).  The keypoints also stay on the device for
+        ``describe()``."""
+        L = capi.lib()
+        if candidates is None:
+            n_cand = ctypes.c_size_t()
+            capi.check(L.oc_hip_sift3d_candidate_count(self._h, ctypes.byref(n_cand)))   # (the list stays where it is)
+            ptr, count, mem_in, keep = None, n_cand.value, capi.HOST, None
+        else:
+            ptr, count, mem_in, keep = self._records(candidates, self.CANDIDATE, "orient")
+            if mem_in == capi.DEVICE:
+                self._adopt_stream_of(candidates)
+                on_device = True
+        n = ctypes.c_size_t()
+        if on_device:
+            import torch
+            dev = keep.device if keep is not None and _is_torch(keep) else torch.device("cuda", self._device)
+            out = torch.empty((count, 18), dtype=torch.int32, device=dev)
+            status = torch.empty(count, dtype=torch.int32, device=dev) if with_status else None
+            sums = torch.empty((count, 9), dtype=torch.float32, device=dev) if with_status else None
+            p = [ctypes.c_void_p(t.data_ptr()) if t is not None and count else None for t in (out, status, sums)]
+            mem = capi.DEVICE
+        else:
+            out = np.zeros(count, dtype=self.KEYPOINT)
+            status = np.zeros(count, np.int32) if with_status else None
+            sums = np.zeros((count, 9), np.float32) if with_status else None
+            p = [ctypes.c_void_p(a.ctypes.data) if a is not None and count else None for a in (out, status, sums)]
+            mem = capi.HOST
+        capi.check(L.oc_hip_sift3d_orient(self._h, ptr, count, mem_in, p[0], count, ctypes.byref(n), p[1], p[2], mem))
+        self._kp_count = n.value
+        out = out[:n.value]
+        return (out, status, sums) if with_status else out
+
+    def describe(self, keypoints=None, out=None):
+        """constructDescriptor (src/oc_sift.cpp:1051-1249): (n, 768) float32.  ``keypoints``: None = the output of the last
+        ``orient``, which is on the device; a ``KEYPOINT`` array; or a CUDA int32 tensor (n, 18).  ``out``: a CUDA float32 tensor
+        (n, 768) to fill -- usable as it is by ``DescriptorMatcher.set_descriptors``; without it a NumPy array comes back, or a new
+        tensor when a tensor went in.  Process a long list in chunks: a million descriptors are 3 GB."""
+        if keypoints is None:
+            ptr, count, mem_in, keep = None, self._kp_count, capi.HOST, None
+        else:
+            ptr, count, mem_in, keep = self._records(keypoints, self.KEYPOINT, "describe")
+            if mem_in == capi.DEVICE:
+                self._adopt_stream_of(keypoints)
+        if out is None and mem_in == capi.DEVICE:
+            import torch
+            out = torch.empty((count, self.DESCRIPTOR_LENGTH), dtype=torch.float32, device=keep.device)
+        if out is None:
+            out = np.zeros((count, self.DESCRIPTOR_LENGTH), np.float32)
+        if tuple(out.shape) != (count, self.DESCRIPTOR_LENGTH):
+            raise ValueError("describe: the output must have shape (%d, %d)" % (count, self.DESCRIPTOR_LENGTH))
+        if _is_torch(out):
+            optr, mem, _ = _buf(out)
+        else:
+            if out.dtype != np.float32 or not out.flags.c_contiguous:
+                raise ValueError("describe: the output must be a contiguous float32 array")
+            optr, mem = ctypes.c_void_p(out.ctypes.data), capi.HOST
+        capi.check(capi.lib().oc_hip_sift3d_describe(self._h, ptr, count, mem_in, optr if count else None, mem))
+        return out
+
+
+class SIFT3D:
+    """SIFT3D() -- SIFT3D::compute (src/oc_sift.cpp:234-293) end to end on the GPU: two extractions (``SIFT3DScaleSpace``: pyramids,
+    extrema, orientation, descriptors) and the brute-force matching of ``DescriptorMatcher``; descriptors go from one to the other
+    as device blocks.  ``compute(ref, tar)`` returns the matched ``coor_img`` pairs, (n, 3) float32 (x, y, z) each, in the order
+    monodirectionalMatch (default, as :285) or bidirectionalMatch gives them.  Volumes are (z, y, x) float32."""
+
+    def __init__(self, device=0):
+        self._device = int(device)
+        self.extractor = SIFT3DScaleSpace(device)
+        self.matcher = DescriptorMatcher(SIFT3DScaleSpace.DESCRIPTOR_LENGTH, 0.85, device)
+        self.ref_keypoints = self.tar_keypoints = None
+
+    def close(self):
+        self.extractor.close()
+        self.matcher.close()
+
+    def set_config(self, **settings):
+        """Any of n_octave_layers, min_dimension, alpha, sigma_source, sigma_base (``SIFT3DScaleSpace.set_config``) and beta, gamma,
+        gradient_threshold, truncate_threshold (``set_feature_config``); what is not named takes the reference's default."""
+        front = {k: settings.pop(k) for k in ("n_octave_layers", "min_dimension", "alpha", "sigma_source", "sigma_base") if k in settings}
+        self.extractor.set_config(**front)
+        self.extractor.set_feature_config(**settings)
+
+    def set_physical_unit(self, unit_x, unit_y, unit_z):
+        self.extractor.set_physical_unit(unit_x, unit_y, unit_z)
+
+    def set_matching_ratio(self, ratio):
+        self.matcher.set_ratio(ratio)
+
+    def extract(self, volume):
+        """(keypoints as a ``KEYPOINT`` array, descriptors as a CUDA tensor (n, 768)) of one volume"""
+        import torch
+        s = self.extractor
+        s.set_volume(volume)
+        s.build()
+        kp = s.orient()
+        desc = torch.empty((len(kp), s.DESCRIPTOR_LENGTH), dtype=torch.float32, device=torch.device("cuda", self._device))
+        s.describe(None, out=desc)
+        return kp, desc
+
+    def compute(self, ref, tar, bidirectional=False):
+        self.ref_keypoints, ref_desc = self.extract(ref)
+        self.tar_keypoints, tar_desc = self.extract(tar)
+        self.matcher.set_descriptors(0, ref_desc)
+        self.matcher.set_descriptors(1, tar_desc)
+        ri, ti = self.matcher.match(DescriptorMatcher.BIDIRECTIONAL if bidirectional else DescriptorMatcher.MONODIRECTIONAL)
+        ri, ti = ri.cpu().numpy(), ti.cpu().numpy()
+        return self.ref_keypoints["coor_img"][ri], self.tar_keypoints["coor_img"][ti]
 
 
 class RegionFit:
