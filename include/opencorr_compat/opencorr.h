@@ -3,6 +3,7 @@
 #pragma once
 #include "oc_deformation.h"
 #include "oc_engines.h"
+#include "oc_feature_affine.h"
 #include "oc_feature_detect.h"
 #include "oc_feature_match.h"
 #include "oc_io.h"

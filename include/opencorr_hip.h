@@ -86,7 +86,8 @@ typedef enum oc_hip_kind {
     OC_HIP_CALIBRATION = 11,
     OC_HIP_STEREOVISION = 12,
     OC_HIP_MATCHER = 13,
-    OC_HIP_SIFT3D = 14
+    OC_HIP_SIFT3D = 14,
+    OC_HIP_FEATURE_AFFINE = 15
 } oc_hip_kind;
 
 #define OC_HIP_POI2D_BYTES 100
@@ -632,6 +633,65 @@ int oc_hip_sift3d_orient(oc_hip_engine* engine, const oc_hip_sift3d_candidate* c
  * million keypoints are 3 GB. */
 int oc_hip_sift3d_describe(oc_hip_engine* engine, const oc_hip_sift3d_keypoint* keypoints, size_t n, int keypoints_memory,
                            float* descriptors, int memory);
+
+/* ---- FeatureAffine2D / FeatureAffine3D: the keypoint-guided affine initial guess ---- */
+/* src/oc_feature_affine.{h,cpp}: per POI the matched keypoints inside the search radius (the neighbor_number_min nearest when
+ * fewer are found), a RANSAC loop of affine fits over samples of them, and the least-squares affine map of the largest
+ * consensus set as the POI's first-order deformation.  The reference seeds std::mt19937_64 from std::random_device and walks
+ * nanoflann's result order, so its output differs from run to run; this engine is deterministic.  The contract:
+ * 1. Candidates: every reference keypoint with d2 < r * r, d2 the float32 sum dx * dx + dy * dy (+ dz * dz) in that order and
+ *    r * r rounded to float, in the order of Strain's walk (the 3 x 3 (x 3) block of grid cells row-major, ascending keypoint
+ *    index inside a cell); fewer than neighbor_number_min (but at least sample_number): the neighbor_number_min nearest by
+ *    ascending (d2, index) (:204-221 / :461-478).  Fewer than sample_number: zncc = -1, the record otherwise untouched.
+ * 2. Coordinates are taken relative to the POI in float32 (:226-230 / :481-485).
+ * 3. The sample of trial t = 0, 1, ... is a partial Fisher-Yates over the candidate positions 0 ... n-1 that starts from the
+ *    identity every trial: for j = 0 ... s-1, k = j + (uint32)(((h >> 32) * (uint64)(n - j)) >> 32), swap positions j and k,
+ *    h = splitmix64(base + ((uint64)t << 8 | j)), base = splitmix64(seed ^ (bits(x) | (uint64)bits(y) << 32)), in 3D
+ *    base = splitmix64(base ^ bits(z)); x, y, z are the coordinates the POI came with.  A POI's record therefore does not
+ *    depend on where it stands in the queue or on how the queue is split.
+ * 4. Sample solve and final fit are one routine: the normal equations of [x y (z) 1] X = [x' y' (z')] accumulated in double
+ *    over the rows in the order given (sample order; candidate order for the final fit), Gaussian elimination with partial
+ *    pivoting in double (first largest |entry| of the column wins; a pivot below 2^-40 times the largest |entry| of A^T A:
+ *    singular; rows are scaled by 1.0 / pivot), X rounded to float32 once.  The reference calls Eigen's float
+ *    colPivHouseholderQr: a stated deviation.  A singular sample gives an empty consensus set and the trial counts; a
+ *    singular final fit gives zncc = -2.
+ * 5. Consensus (:262-282 / :519-543): the reference's float32 expressions in its order, every operation rounded on its own,
+ *    strict < error_threshold; the set is kept in candidate order; its error sum is float32, candidate position j added by
+ *    lane j % 64 in ascending j, the 64 partials combined by an xor butterfly with offsets 1, 2, ... 32; mean = sum / count
+ *    (NaN for an empty set, which compares false); the replacement of the largest set and the exit rule are the reference's
+ *    (:284-292 / :545-551, the mean being the current trial's).
+ * 6. Output (:296-330 / :555-596): fewer than ndim + 1 inliers: zncc = -2; otherwise the deformation, result.iteration = trials,
+ *    result.feature = inliers (POI3D: the float behind convergence, src/oc_poi.h:93-99) and zncc = 0.
+ * 7. Self-adaptive subsets, 2D (:128-179): the subset_feature_min nearest keypoints, their bounding box, the reference's update
+ *    of the POI's x, y and subset_radius; relative coordinates after the update, the generator's key before it.
+ * "arith_fma" is refused: this engine has one arithmetic.  oc_hip_set_devices is refused (OC_HIP_ERR_UNSUPPORTED).
+ * Limits, OC_HIP_ERR_UNSUPPORTED: sample_number outside [ndim + 1, 8], trial_number outside [1, 1024], neighbor_number_min or
+ * subset_feature_min above 64, more than 2^31-1 keypoints, a POI with more than 16384 keypoints inside the radius (compute
+ * names the POI and writes nothing).  A queue with a NaN POI coordinate: OC_HIP_ERR_INVALID, nothing is written. */
+/* FeatureAffine2D(radius_x, radius_y, thread_number) :34-55 (ndim 2; radius_z ignored) / FeatureAffine3D(radius_x, radius_y,
+ * radius_z, thread_number) :357-374 (ndim 3), with their defaults: search radius sqrt(rx^2 + ry^2 (+ rz^2)), neighbor_number_min
+ * 7 / 16, error_threshold 1.5 / 3.2, sample_number 3 / 4, trial_number 20 / 32. */
+int oc_hip_feature_affine_create(int ndim, int radius_x, int radius_y, int radius_z, int device, oc_hip_engine** out);
+/* setSearch :81-85 / :400-404.  A new radius needs oc_hip_feature_affine_prepare again. */
+int oc_hip_feature_affine_set_search(oc_hip_engine* engine, float neighbor_search_radius, int neighbor_number_min);
+/* setRansacConfig :87-90 / :406-409 (RansacConfig: trial_number, sample_mumber, error_threshold, src/oc_feature_affine.h:26-31) */
+int oc_hip_feature_affine_set_ransac(oc_hip_engine* engine, int trial_number, int sample_number, float error_threshold);
+/* the seed of the sample generator (0 at creation); the reference has none (:241-242 / :496-497) */
+int oc_hip_feature_affine_set_seed(oc_hip_engine* engine, unsigned long long seed);
+/* DIC::setSelfAdaptive + setSubsetAdjustment :92-96 + the size of the reference image (:130-133); FeatureAffine2D only */
+int oc_hip_feature_affine_set_self_adaptive(oc_hip_engine* engine, int enable, int feature_min, int radius_min, int width, int height);
+/* setKeypointPair :98-102 / :411-415: `count` matched pairs, packed ndim floats per point, where `memory` says.  Copied. */
+int oc_hip_feature_affine_set_keypoints(oc_hip_engine* engine, const float* ref, const float* tar, size_t count, int memory);
+/* setKeypointPair from the pairs oc_hip_matcher_match returned: pair k is (ref_kp[ref_idx[k]], tar_kp[tar_idx[k]]), the
+ * keypoint arrays packed ndim floats per point; everything on the device (memory must be OC_HIP_DEVICE), gathered there.
+ * A negative index (the matcher's -1, a stale list) is refused with OC_HIP_ERR_INVALID and nothing is read through it; the engine
+ * then holds no keypoints.  Indices are not checked against the arrays' lengths, which this call does not know. */
+int oc_hip_feature_affine_set_matched(oc_hip_engine* engine, const float* ref_kp, const float* tar_kp, const int* ref_idx,
+                                      const int* tar_idx, size_t n_pairs, int memory);
+/* prepare :104-116 / :417-429: the grid over the reference keypoints */
+int oc_hip_feature_affine_prepare(oc_hip_engine* engine);
+/* compute(std::vector<POI2D>&) :334-342 / compute(std::vector<POI3D>&) :600-608, in place */
+int oc_hip_feature_affine_compute(oc_hip_engine* engine, void* pois, size_t count, size_t stride_bytes, int memory);
 
 /* ---- introspection (tests, bench, profiling) ------------------------------ */
 int oc_hip_get_kind(const oc_hip_engine* engine, int* kind);

@@ -696,6 +696,7 @@ int oc_hip_set_images2d(oc_hip_engine* e, const float* ref, const float* tar, in
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: the SIFT3D scale space takes one volume (oc_hip_sift3d_set_volume)");
+    if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: a FeatureAffine engine holds no images (oc_hip_feature_affine_set_keypoints)");
     if (e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images2d called on a 3D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null image pointer");
     if (height < 5 || width < 5) return fail(OC_HIP_ERR_INVALID, "image too small: %d x %d", width, height);
@@ -737,6 +738,7 @@ int oc_hip_set_images3d(oc_hip_engine* e, const float* ref, const float* tar, in
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: the SIFT3D scale space takes one volume (oc_hip_sift3d_set_volume)");
+    if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: a FeatureAffine engine holds no images (oc_hip_feature_affine_set_keypoints)");
     if (!e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images3d called on a 2D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null volume pointer");
     if (dim_x < 15 || dim_y < 15 || dim_z < 15)
@@ -826,6 +828,7 @@ int oc_hip_set_devices(oc_hip_engine* e, const int* device_ids, int n_devices) {
     if (n_devices > 1 && (e->kind == OC_HIP_STRAIN || e->kind == OC_HIP_REGION_FIT))
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Strain / RegionFit need every neighbour of a POI and stay on one device");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a SIFT3D scale space stays on the device it was created for");
+    if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a FeatureAffine engine needs every keypoint around a POI and has no device groups");
     if (n_devices > 1 && e->is_matcher())
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a descriptor matcher needs every candidate of a query and stays on one device");
     int ndev = 0;
@@ -1092,6 +1095,7 @@ static int compute_impl(oc_hip_engine* e, void* pois, const float* offsets, size
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT3D scale space has no POI queue (oc_hip_sift3d_build / oc_hip_sift3d_detect)");
+    if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a FeatureAffine engine computes through oc_hip_feature_affine_compute");
     if (count == 0) return OC_HIP_OK;
     if (!pois) return fail(OC_HIP_ERR_INVALID, "null POI buffer");
     if (stride_bytes < e->poi_bytes() || (stride_bytes & 3))
@@ -1142,6 +1146,8 @@ int oc_hip_compute_chain(oc_hip_engine* const* engines, int n_engines, void* poi
         if (engines[i]->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: a descriptor matcher has no POI queue");
     for (int i = 0; i < n_engines; i++)
         if (engines[i]->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: the SIFT3D scale space has no POI queue");
+    for (int i = 0; i < n_engines; i++)
+        if (engines[i]->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: a FeatureAffine engine computes through oc_hip_feature_affine_compute, before the chain");
     if (n_engines == 1) return compute_impl(engines[0], pois, nullptr, count, stride_bytes, memory);
     oc_hip_engine* lead = engines[0];
     for (int i = 1; i < n_engines; i++) {

@@ -249,6 +249,11 @@ struct DeviceState {
     size_t st_count = 0;  // queue length the grid was prepared for (0 = not prepared)
     ochip::StrainGrid st_grid{};
     DevBuf st_box, st_counts, st_start, st_cursor, st_slots, st_order, st_recs, st_fallback;
+    // FeatureAffine (capi_feature_affine.hip): the engine's copy of the matched keypoints (packed, fa_ndim floats per point), the
+    // verdict words of the count pass and the global slices of candidate lists beyond the LDS part.  The grid over the reference
+    // keypoints lives in the st_* buffers above (st_count = keypoints it was prepared for).
+    size_t fa_count = 0;
+    DevBuf fa_ref, fa_tar, fa_verdict, fa_scratch;
     DevBuf cal_map_x, cal_map_y, cal_stage;  // Calibration: the undistortion map
     // Descriptor matcher: side 0 = reference, 1 = target.  HOST descriptors are copied into mt_desc, DEVICE ones are used in place (mt_ext).
     size_t mt_count[2] = {0, 0};
@@ -316,6 +321,13 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
     // Descriptor matcher (capi_match.hip; SIFT3D::bruteforceMatch and the two match modes, src/oc_sift.cpp:625-674, 1251-1487)
     int mt_dim = 0;
     float mt_ratio = 0.f;
+    // FeatureAffine2D/3D (capi_feature_affine.hip; src/oc_feature_affine.cpp:34-55, 357-374): search, RANSAC, seed, self-adaptive subsets
+    int fa_ndim = 0;
+    float fa_radius = 0.f, fa_threshold = 0.f;
+    int fa_nmin = 0, fa_samples = 0, fa_trials = 0;
+    unsigned long long fa_seed = 0;
+    bool fa_adaptive = false;
+    int fa_feature_min = 14, fa_radius_min = 10, fa_width = 0, fa_height = 0;
     // SIFT3D scale space (capi_sift3d.hip; SIFT3D::createGaussianPyramid, createDogPyramid, detectExtrema, src/oc_sift.cpp:676-847):
     // the settings, the volume's dims, the plan of the last build (host/sift3d_plan.h) and max_abs of every DoG layer
     ochip_host::Sift3dSettings sf_cfg;
@@ -354,6 +366,7 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
 
     bool is_matcher() const { return kind == OC_HIP_MATCHER; }
     bool is_sift3d() const { return kind == OC_HIP_SIFT3D; }
+    bool is_feature_affine() const { return kind == OC_HIP_FEATURE_AFFINE; }
     bool is3d() const { return kind == OC_HIP_FFTCC3D || kind == OC_HIP_ICGN3D1; }
     bool is_iclm() const { return kind == OC_HIP_ICLM2D1 || kind == OC_HIP_ICLM2D2; }
     bool is_icgn2d() const { return kind == OC_HIP_ICGN2D1 || kind == OC_HIP_ICGN2D2 || is_iclm(); }

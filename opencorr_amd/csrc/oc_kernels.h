@@ -155,6 +155,44 @@ hipError_t launch_strain2ds_compute(float* pois, int stride_floats, size_t count
                                     const unsigned* start, const unsigned* order, void* recs, unsigned* fallback,
                                     hipStream_t stream);
 
+// ---- feature_affine.hip -------------------------------------------------------
+// FeatureAffine2D/3D::compute (src/oc_feature_affine.cpp): the seeded RANSAC affine fit over the matched keypoints around a POI.
+// The grid over the reference keypoints is Strain's (launch_strain_bbox / strain_make_grid / launch_strain_sort on the packed
+// keypoint array, stride ndim floats).  The contract: DESIGN.md section 4.12.
+struct FeatureAffineParams {
+    float radius2;           // neighbor_search_radius squared, rounded to float
+    float error_threshold;   // RansacConfig::error_threshold
+    int neighbor_min;        // neighbor_number_min
+    int sample_number;       // RansacConfig::sample_mumber, ndim + 1 ... 8
+    int trial_number;        // RansacConfig::trial_number, 1 ... 1024
+    int self_adaptive;       // 2D only (src/oc_feature_affine.cpp:128-179)
+    int feature_min;         // subset_feature_min
+    int radius_min;          // subset_radius_min
+    float width, height;     // of the reference image (:130-133)
+    unsigned long long seed;
+};
+constexpr int kFeatureAffineListLds = 1024;   // candidates of a POI kept in LDS; the rest lives in a global slice
+constexpr int kFeatureAffineListMax = 16384;  // largest candidate count of a POI
+constexpr int kFeatureAffineMaxSlots = 1024;  // waves of a launch that needs global slices (a slice: 2 ndim arrays of the launch's largest list beyond the LDS part)
+// {ref xyz, tar xyz, keypoint index} in cell order.  recs: count * 32 bytes
+hipError_t launch_feature_affine_gather(int ndim, const float* ref, const float* tar, size_t count, const unsigned* order, void* recs,
+                                        hipStream_t stream);
+// out_ref / out_tar[k] = ref_kp[ref_idx[k]] / tar_kp[tar_idx[k]], packed ndim floats per point.  *negative (device) = the first
+// pair with a negative index (0xffffffff: none); such a pair reads nothing
+hipError_t launch_feature_affine_pairs(int ndim, const float* ref_kp, const float* tar_kp, const int* ref_idx, const int* tar_idx,
+                                       size_t n_pairs, float* out_ref, float* out_tar, unsigned* negative, hipStream_t stream);
+// Candidate count of every POI (what the radius walk of compute finds; 0 in self-adaptive mode, whose list is the KNN's).
+// verdict[0] = the largest count, verdict[1] = smallest index of a POI with more than kFeatureAffineListMax candidates,
+// verdict[2] = smallest index of a POI with a NaN coordinate (0xffffffff: none).  Writes nothing else.
+hipError_t launch_feature_affine_count(int ndim, const float* pois, int stride_floats, size_t count, const StrainGrid& g,
+                                       const FeatureAffineParams& P, const unsigned* start, const void* recs, unsigned* verdict,
+                                       hipStream_t stream);
+// bytes of the global slices a launch over `count` POIs needs when the largest candidate count is `max_candidates`
+size_t feature_affine_scratch_bytes(int ndim, size_t count, unsigned max_candidates);
+hipError_t launch_feature_affine_compute(int ndim, float* pois, int stride_floats, size_t count, const StrainGrid& g,
+                                         const FeatureAffineParams& P, const unsigned* start, const void* recs,
+                                         unsigned max_candidates, float* scratch, hipStream_t stream);
+
 // float offsets inside a POI2DS, the stereo record (src/oc_poi.h:53-60, 73-90, 140-183): x, y | u, v, w | r1r2, r1t1, r1t2 zncc,
 // r2, t1, t2 | ref_coor | tar_coor | six strains | subset_radius
 namespace poi2ds {

@@ -1076,6 +1076,139 @@ class RegionFit:
         return pois
 
 
+class _FeatureAffine(_Handle):
+    """What FeatureAffine2D and FeatureAffine3D share (src/oc_feature_affine.h): the keypoint-guided RANSAC affine initial
+    guess.  ``set_keypoint_pair(ref_kp, tar_kp)`` takes the matched keypoints ((m, ndim) float32, NumPy or CUDA tensor;
+    copied), ``prepare()`` builds the neighbour search over the reference keypoints, ``compute(pois)`` writes the
+    first-order deformation, ``result.iteration`` (trials), ``result.feature`` (inliers; POI3D: float 21) and ``zncc``
+    (0, -1 too few keypoints, -2 no consensus) of every POI in place.  Deterministic: the samples come from a counter-based
+    generator keyed by ``set_seed`` and the POI's coordinates."""
+    _ndim = 0
+
+    def _create(self, radii, thread_number, device):
+        super().__init__(device)
+        self.thread_number = thread_number
+        capi.check(capi.lib().oc_hip_feature_affine_create(self._ndim, int(radii[0]), int(radii[1]), int(radii[2]), int(device),
+                                                           ctypes.byref(self._h)))
+        r2 = sum(int(r) * int(r) for r in radii[:self._ndim])
+        self._radius = float(np.sqrt(np.float32(r2)))
+
+    def get_ransac_config(self):
+        return dict(self._ransac)
+
+    def get_search_radius(self):
+        return self._radius
+
+    def get_neighbor_min(self):
+        return self._nmin
+
+    def set_search(self, neighbor_search_radius, neighbor_number_min):
+        capi.check(capi.lib().oc_hip_feature_affine_set_search(self._h, float(neighbor_search_radius), int(neighbor_number_min)))
+        self._radius, self._nmin = float(np.float32(neighbor_search_radius)), int(neighbor_number_min)
+
+    def set_ransac_config(self, trial_number, sample_number, error_threshold):
+        """RansacConfig: trial_number (1 ... 1024), sample_mumber (ndim + 1 ... 8), error_threshold."""
+        capi.check(capi.lib().oc_hip_feature_affine_set_ransac(self._h, int(trial_number), int(sample_number), float(error_threshold)))
+        self._ransac = dict(trial_number=int(trial_number), sample_number=int(sample_number), error_threshold=float(error_threshold))
+
+    def set_seed(self, seed):
+        capi.check(capi.lib().oc_hip_feature_affine_set_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_tuning(self, key, value):
+        capi.check(capi.lib().oc_hip_set_tuning(self._h, key.encode(), int(value)))
+
+    def _points(self, x, what):
+        if not _is_torch(x):
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        elif not x.is_contiguous():
+            x = x.contiguous()
+        if len(x.shape) != 2 or x.shape[1] != self._ndim:
+            raise ValueError("%s: keypoints must have shape (count, %d)" % (what, self._ndim))
+        return x
+
+    def set_keypoint_pair(self, ref_kp, tar_kp):
+        ref_kp, tar_kp = self._points(ref_kp, "set_keypoint_pair"), self._points(tar_kp, "set_keypoint_pair")
+        if ref_kp.shape[0] != tar_kp.shape[0] or _is_torch(ref_kp) != _is_torch(tar_kp):
+            raise ValueError("set_keypoint_pair: the two sides differ in length or memory space")
+        self._adopt_stream_of(ref_kp)
+        pr, mem, _ = _buf(ref_kp)
+        pt, _, _ = _buf(tar_kp)
+        capi.check(capi.lib().oc_hip_feature_affine_set_keypoints(self._h, pr, pt, ref_kp.shape[0], mem))
+
+    def set_matched_pairs(self, ref_kp, tar_kp, ref_idx, tar_idx):
+        """The pairs ``DescriptorMatcher.match`` returned, gathered on the device: pair k is (ref_kp[ref_idx[k]],
+        tar_kp[tar_idx[k]]).  CUDA tensors: keypoints (count, ndim) float32, indices int32.  A negative index is refused
+        (the engine then holds no keypoints); indices are not checked against the keypoint counts."""
+        import torch
+        ref_kp, tar_kp = self._points(ref_kp, "set_matched_pairs"), self._points(tar_kp, "set_matched_pairs")
+        for t in (ref_kp, tar_kp, ref_idx, tar_idx):
+            if not _is_torch(t) or not t.is_cuda:
+                raise ValueError("set_matched_pairs: every array is a CUDA tensor")
+        if ref_idx.dtype != torch.int32 or tar_idx.dtype != torch.int32 or ref_idx.shape != tar_idx.shape or ref_idx.dim() != 1:
+            raise ValueError("set_matched_pairs: the index lists are int32 vectors of one length")
+        ref_idx, tar_idx = ref_idx.contiguous(), tar_idx.contiguous()
+        self._adopt_stream_of(ref_kp)
+        capi.check(capi.lib().oc_hip_feature_affine_set_matched(self._h, ctypes.c_void_p(ref_kp.data_ptr()), ctypes.c_void_p(tar_kp.data_ptr()),
+                                                                ctypes.c_void_p(ref_idx.data_ptr()), ctypes.c_void_p(tar_idx.data_ptr()),
+                                                                ref_idx.shape[0], capi.DEVICE))
+
+    def prepare(self):
+        capi.check(capi.lib().oc_hip_feature_affine_prepare(self._h))
+
+    def compute(self, pois):
+        self._adopt_stream_of(pois)
+        p, n, stride, mem, _ = self._rows(pois, capi.POI2D_FLOATS if self._ndim == 2 else capi.POI3D_FLOATS, "compute")
+        capi.check(capi.lib().oc_hip_feature_affine_compute(self._h, p, n, stride, mem))
+        return pois
+
+
+class FeatureAffine2D(_FeatureAffine):
+    """FeatureAffine2D(radius_x, radius_y, thread_number) -- src/oc_feature_affine.h:37-70, src/oc_feature_affine.cpp:34-55."""
+    _ndim = 2
+
+    def __init__(self, radius_x, radius_y, thread_number=1, device=0):
+        self._create((radius_x, radius_y, 0), thread_number, device)
+        self._nmin = 7
+        self._ransac = dict(trial_number=20, sample_number=3, error_threshold=1.5)
+        self._adjust = (14, 10)
+        self._size = None
+        self._adaptive = False
+
+    def set_images(self, height, width):
+        """The reference reads ref_img->width / height in self-adaptive mode (:130-133): the size is all this engine needs."""
+        self._size = (int(height), int(width))
+        self._push_adaptive()
+
+    def set_self_adaptive(self, is_self_adaptive):
+        self._adaptive = bool(is_self_adaptive)
+        self._push_adaptive()
+
+    def set_subset_adjustment(self, feature_min, radius_min):
+        self._adjust = (int(feature_min), int(radius_min))
+        self._push_adaptive()
+
+    def _push_adaptive(self):
+        if self._adaptive and self._size is None:
+            return  # (compute refuses below until the size is known)
+        h, w = self._size or (0, 0)
+        capi.check(capi.lib().oc_hip_feature_affine_set_self_adaptive(self._h, 1 if self._adaptive else 0, self._adjust[0], self._adjust[1], w, h))
+
+    def compute(self, pois):
+        if self._adaptive and self._size is None:
+            raise ValueError("FeatureAffine2D: self-adaptive subsets need set_images(height, width)")
+        return super().compute(pois)
+
+
+class FeatureAffine3D(_FeatureAffine):
+    """FeatureAffine3D(radius_x, radius_y, radius_z, thread_number) -- src/oc_feature_affine.h:77-106, src/oc_feature_affine.cpp:357-374."""
+    _ndim = 3
+
+    def __init__(self, radius_x, radius_y, radius_z, thread_number=1, device=0):
+        self._create((radius_x, radius_y, radius_z), thread_number, device)
+        self._nmin = 16
+        self._ransac = dict(trial_number=32, sample_number=4, error_threshold=3.2)
+
+
 class FFTCC3D(_Engine):
     """FFTCC3D(rx, ry, rz, thread_number) -- src/oc_fftcc.h:75-89."""
     _ndim = 3
