@@ -1,23 +1,37 @@
-"""A plain float64 model of ICGN3D1::compute(POI3D*) and ICGN2D2::compute(POI2D*), one POI at a time.
+"""Plain float64 models of the iterative solvers, one POI at a time: ICGN3D1::compute(POI3D*), ICGN2D2::compute(POI2D*),
+ICGN2D1::compute(POI2D*) with and without a centre offset, ICLM2D1 / ICLM2D2::compute(POI2D*) and NR2D1::compute(POI2D*).
 
-TEST INFRASTRUCTURE ONLY.  Written from the algorithm (inverse-compositional Gauss-Newton with a ZNSSD criterion), not
-from the oracle's or the reference's loops: NumPy float64 throughout, ``numpy.linalg`` for the two inverses, NumPy's own
-reductions for every sum.  What enters as DATA (pinned elsewhere: tests/test_oracle_bspline_scipy.py,
-tests/test_oracle_vs_ref.py) is the reference image / volume, its gradients and the target's B-spline coefficients, taken
-from ``oracle.Prepared3D`` / ``oracle.Prepared2D`` and converted to float64; the 64-tap tricubic sum and the 16-term
-bicubic polynomial are evaluated here.
+TEST INFRASTRUCTURE ONLY.  Written from the algorithms (inverse-compositional Gauss-Newton and Levenberg-Marquardt, forward-
+additive Newton-Raphson, all with a ZNSSD criterion), not from the oracle's or the reference's loops: NumPy float64
+throughout, ``numpy.linalg`` for the inverses, NumPy's own reductions for every sum.  What enters as DATA (pinned elsewhere:
+tests/test_oracle_bspline_scipy.py, tests/test_oracle_vs_ref.py) is the reference image / volume, its gradients and the
+target's B-spline coefficients (NR2D1: the three tables of the target), taken from ``oracle.Prepared3D`` / ``Prepared2D`` /
+``PreparedNR2D`` and converted to float64; the 64-tap tricubic sum and the 16-term bicubic polynomial are evaluated here.
 
-Reference lines cited as ``icgn:N`` = src/oc_icgn.cpp, ``def:N`` = src/oc_deformation.cpp, ``bsp:N`` =
-src/oc_cubic_bspline.cpp, ``sub:N`` = src/oc_subset.cpp of the reference.
+Reference lines cited as ``icgn:N`` = src/oc_icgn.cpp, ``iclm:N`` = src/oc_iclm.cpp, ``nr:N`` = src/oc_nr.cpp, ``def:N`` =
+src/oc_deformation.cpp, ``bsp:N`` = src/oc_cubic_bspline.cpp, ``sub:N`` = src/oc_subset.cpp of the reference.
 
-``flaw=`` plants ONE named mistake (tests/test_model64_cpu.py's sharpness test: a flawed model must put the oracle outside
-the bars below, otherwise the bars are no evidence):
+``flaw=`` plants ONE named mistake (tests/test_model64_cpu.py's sharpness tests: a flawed model must put the oracle outside
+the bars below, otherwise the bars are no evidence).  The Gauss-Newton models (FLAWS):
     "update_side"  W(dp)^-1 * W(p) instead of W(p) * W(dp)^-1
     "sd_column"    the steepest-descent column of ux without its x_local factor (it then repeats the column of u: the
                    Hessian is singular and the increment not finite -- the crude form of the mistake)
     "sd_origin"    the x_local of that column counted from the subset's corner instead of its centre (the subtle form: the
                    columns span the same space, the fit is as good, the parameters mean something else)
     "norm_ratio"   the error image without the |R| / |T| factor
+IC-LM (LM_FLAWS):
+    "lm_zero"      no damping at all (lambda = 0)
+    "lm_diag"      the damping on diag(H) (Marquardt's form) instead of on the identity
+    "lm_swap"      alpha and beta swapped: lambda grows on accepted steps
+    "lm_keep0"     znssd0 not replaced when a step is accepted
+    "lm_norm_accepted"  the convergence norm taken from accepted increments only
+NR (NR_FLAWS):
+    "nr_hessian_once"   the Hessian of the first iteration kept
+    "nr_grad_at_ref"    the target's gradient tables sampled at the unwarped positions
+    "nr_compose"        a compositional update W(p) * W(dp) instead of p + dp
+
+IC-LM branch ties: see _iterate_lm.  Where float32 cannot order znssd and znssd0 the model follows both branches, and a
+candidate is compared with the path it took (select_path); no record is set aside.
 """
 import numpy as np
 
@@ -27,17 +41,20 @@ FLAWS = ("update_side", "sd_column", "sd_origin", "norm_ratio")
 # Measured distances of the COMPILED REFERENCE from this model, and the bars derived from them (bar = 4 x distance).
 #
 # Build: the reference's own src/*.cpp compiled unmodified over the stand-in Eigen / FFTW headers (oracle/_ref/liboc_ref.so,
-# `make -C oracle ref`, g++ -O2 -ffp-contract=off), x86-64.  Cases: exactly cases3d() and cases2d2() below (3D: the
-# 72 x 76 x 80 pair, radii (8,8,8) and (5,7,6), 27 grid + 10 off-grid POIs, FFTCC3D guesses and their noisy copy;
-# 3DE: r = 16 on the 96 x 100 x 104 pair, 8 POIs; 2D2: the 300 x 320 second-order pair, radii (20,20) and (12,16), 72 grid
-# + 10 off-grid POIs, FFTCC2D guesses and their noisy copy).  Regenerate with `python tests/icgn_model64.py --measure`
-# (needs the reference build); tests/test_model64_cpu.py::test_reference_within_measured_distances keeps them honest.
+# `make -C oracle ref`, g++ -O2 -ffp-contract=off), x86-64.  Cases: exactly all_cases() below (3D: the 72 x 76 x 80 pair, radii
+# (8,8,8) and (5,7,6), 27 grid + 10 off-grid POIs, FFTCC3D guesses and their noisy copy; 3DE: r = 16 on the 96 x 100 x 104 pair,
+# 8 POIs; 2D2: the 300 x 320 second-order pair, radii (20,20) and (12,16), 72 grid + 10 off-grid POIs, FFTCC2D guesses and their
+# noisy copy; 2D1 / 2D1O / LM1 / LM2 / NR1: the 300 x 320 first-order pair -- 2 degrees of rotation, 1 % stretch -- with 40 grid +
+# 10 off-grid POIs, see cases2d1(), caseslm(), casesnr()).  Regenerate with `python tests/icgn_model64.py --measure` (needs the
+# reference build); tests/test_model64_cpu.py::test_reference_within_measured_distances[_6dof] keep them honest.
+# On the first-order pair the reference converges on every grid POI at every radius pair of every solver, the exempt (7, 9) and
+# (9, 12) aside (there: 97.5 % for ICGN2D1, 92.5 ... 100 % for IC-LM, 100 % for NR2D1); the rotation did not have to come down.
 # The factor 4: the oracle's lane orders and the GPU's fused multiply-adds are other float32 realisations of the same sums
 # (rounding of the same scale, not the same sign), and the maximum is over a few hundred POIs only.
 # Nothing here comes from oracle or GPU output.
 #
 # MEASURED[family][group] = [k = 1, 2, 3, 4, 5, ordinary run]; groups: "disp" (u, v[, w]), "grad" (first-order parameters),
-# "grad2" (2D2: second-order parameters), "conv" (the convergence field), "zncc" (ordinary run only).
+# "grad2" (2D2, LM2: second-order parameters), "conv" (the convergence field), "zncc" (ordinary run only).
 # ---------------------------------------------------------------------------------------------------------------------
 MEASURED = {
     "3D": {"disp": [2.974e-05, 8.846e-06, 3.656e-06, 3.911e-06, 4.104e-06, 4.104e-06],
@@ -50,9 +67,27 @@ MEASURED = {
             "grad": [1.134e-06, 4.562e-07, 3.546e-07, 4.228e-07, 2.839e-07, 4.228e-07],
             "grad2": [7.609e-07, 1.005e-07, 9.464e-08, 1.194e-07, 1.645e-07, 1.194e-07],
             "conv": [3.235e-05, 2.708e-05, 1.219e-05, 8.964e-06, 1.295e-05, 8.964e-06], "zncc": [3.521e-08]},
+    "2D1": {"disp": [1.369e-05, 8.528e-06, 5.132e-06, 4.670e-06, 2.860e-06, 4.670e-06],
+            "grad": [1.909e-06, 1.484e-06, 1.065e-06, 1.266e-06, 9.262e-07, 1.266e-06],
+            "conv": [3.534e-05, 3.228e-05, 9.847e-06, 1.292e-05, 1.200e-05, 1.292e-05], "zncc": [4.260e-08]},
+    "2D1O": {"disp": [4.859e-06, 1.569e-05, 1.528e-05, 1.657e-05, 1.563e-05, 1.657e-05],
+             "grad": [2.250e-07, 3.695e-07, 1.529e-07, 3.464e-07, 2.783e-07, 3.464e-07],
+             "conv": [3.778e-06, 7.412e-06, 4.639e-06, 3.535e-06, 6.461e-06, 3.535e-06], "zncc": [3.121e-08]},
+    "LM1": {"disp": [5.094e-06, 4.859e-06, 2.648e-06, 2.195e-06, 2.809e-06, 2.195e-06],
+            "grad": [7.137e-07, 1.099e-06, 5.254e-07, 5.587e-07, 5.007e-07, 5.007e-07],
+            "conv": [5.400e-06, 8.135e-06, 5.677e-06, 5.246e-06, 8.079e-06, 5.246e-06], "zncc": [3.953e-08]},
+    "LM2": {"disp": [1.258e-04, 1.932e-05, 5.926e-06, 5.926e-06, 7.699e-06, 5.926e-06],
+            "grad": [4.809e-06, 1.625e-06, 9.975e-07, 8.477e-07, 1.176e-06, 8.477e-07],
+            "grad2": [1.971e-06, 3.486e-07, 3.925e-07, 2.193e-07, 3.128e-07, 2.193e-07],
+            "conv": [4.807e-05, 9.992e-05, 2.789e-05, 1.941e-05, 2.141e-05, 1.852e-05], "zncc": [5.202e-08]},
+    "NR1": {"disp": [3.304e-06, 2.173e-06, 2.296e-06, 8.287e-06, 3.718e-06, 2.296e-06],
+            "grad": [7.426e-07, 5.962e-07, 7.339e-07, 6.252e-07, 6.485e-07, 6.252e-07],
+            "conv": [5.211e-06, 6.545e-06, 7.837e-06, 6.474e-06, 1.325e-05, 7.147e-06], "zncc": [3.955e-08]},
 }
-# reference POIs that used the one-iteration exception of the ordinary run, of how many records
-MEASURED_EXCEPTIONS = {"3D": (0, 148), "3DE": (0, 8), "2D2": (0, 328)}
+# reference POIs that used the one-iteration exception of the ordinary run, of how many records.  No record is set aside for an
+# IC-LM branch tie: the model follows both branches there (_iterate_lm).
+MEASURED_EXCEPTIONS = {"3D": (0, 148), "3DE": (0, 8), "2D2": (0, 328),
+                       "2D1": (1, 300), "2D1O": (0, 20), "LM1": (0, 450), "LM2": (0, 450), "NR1": (0, 200)}
 BAR_FACTOR = 4.0
 BARS = {fam: {g: [BAR_FACTOR * d for d in v] for g, v in groups.items()} for fam, groups in MEASURED.items()}
 ORDINARY = 5   # index of the ordinary run in a MEASURED / BARS list ("zncc" has that entry only, at index 0)
@@ -70,6 +105,7 @@ GROUPS = {
         "zncc": ("zncc",)},
     2: {"disp": ("u", "v"), "grad": ("ux", "uy", "vx", "vy"), "grad2": ("uxx", "uxy", "uyy", "vxx", "vxy", "vyy"),
         "conv": ("convergence",), "zncc": ("zncc",)},
+    21: {"disp": ("u", "v"), "grad": ("ux", "uy", "vx", "vy"), "conv": ("convergence",), "zncc": ("zncc",)},   # 2D, 6 DoF
 }
 
 
@@ -314,6 +350,300 @@ def solve2d2(fields, rx, ry, conv, stop, poi, flaw=None):
     return (recs if many else recs[0]), [s[1] for s in states]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The 6-DoF solvers: ICGN2D1 (also with centre offsets), ICLM2D1 / ICLM2D2 and NR2D1.
+# ``iclm:N`` = src/oc_iclm.cpp, ``nr:N`` = src/oc_nr.cpp.  ``runs`` is a list of (conv, stop): one record per entry, from ONE
+# sequence of max(stop) iterations (the iterates do not depend on conv or stop; each run performs a prefix of them).
+# ---------------------------------------------------------------------------------------------------------------------
+ORDER21 = ("u", "ux", "uy", "v", "vx", "vy")                                                         # dp[] of icgn:279-287
+LM_FLAWS = ("lm_zero", "lm_diag", "lm_swap", "lm_keep0", "lm_norm_accepted")
+NR_FLAWS = ("nr_hessian_once", "nr_grad_at_ref", "nr_compose")
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def warp2d1(p):
+    """Deformation2D1::setWarp (def:117-128); p in ORDER21."""
+    u, ux, uy, v, vx, vy = p
+    return np.array([[1 + ux, uy, u], [vx, 1 + vy, v], [0, 0, 1.0]])
+
+
+def unwarp2d1(W):
+    """Deformation2D1::setDeformation() (def:107-115)."""
+    return np.array([W[0, 2], W[0, 0] - 1, W[0, 1], W[1, 2], W[1, 0], W[1, 1] - 1])
+
+
+def _guard2d(out, h, wd, rx, ry):
+    """The entry test shared by all 2D solvers (icgn:160-163, iclm:166-169, nr:165-168), negated so that NaN is rejected."""
+    x, y, zncc, u, v = out[P2["x"]], out[P2["y"]], out[P2["zncc"]], out[P2["u"]], out[P2["v"]]
+    inside = y - ry >= 0 and x - rx >= 0 and y + ry <= h - 1 and x + rx <= wd - 1
+    return bool(inside and abs(u) < wd and abs(v) < h and zncc >= 0)
+
+
+def _subset2d(fields, x, y, rx, ry):
+    """(lx, ly, reference subset zero-meaned, its norm, flat pixel indices): the reference subset sits at the TRUNCATED position
+    (icgn:174-176, 186-187; sub:39-44)."""
+    ly, lx = np.meshgrid(np.arange(-ry, ry + 1.0), np.arange(-rx, rx + 1.0), indexing="ij")
+    lx, ly = lx.ravel(), ly.ravel()
+    ix, iy = int(x) + lx.astype(np.int64), int(y) + ly.astype(np.int64)
+    ref0, ref_norm = _zero_mean(fields.ref[iy, ix])
+    return lx, ly, ref0, ref_norm, (iy, ix)
+
+
+def _sd6(gx, gy, lx, ly, rx, flaw=None):
+    """The six steepest-descent columns in ORDER21 (icgn:191-196)."""
+    cols = [gx, gx * lx, gx * ly, gy, gy * lx, gy * ly]
+    if flaw == "sd_column":
+        cols[1] = cols[0]
+    if flaw == "sd_origin":
+        cols[1] = cols[0] * (lx + rx)
+    return np.stack(cols, axis=1)
+
+
+def _weights(rx, ry, dof, truncated):
+    """Weights of the convergence norm in ORDER21 / ORDER2.  6 DoF: the integers rx^2, ry^2 (icgn:296-304).  12 DoF: r^4 / 4 is
+    truncated to an integer in ICGN2D2 (icgn:837-856) and kept as a float in ICLM2D2 (iclm:671-686)."""
+    rx2, ry2 = rx * rx, ry * ry
+    if dof == 6:
+        return np.array([1, rx2, ry2] * 2, dtype=np.float64)
+    rx4, ry4 = rx2 * rx2 * 0.25, ry2 * ry2 * 0.25
+    if truncated:
+        rx4, ry4 = int(rx4), int(ry4)
+    return np.array([1, rx2, ry2, rx4, rx2 * ry2, ry4] * 2, dtype=np.float64)
+
+
+def _records(out, order, radii, states, left, runs):
+    return [_finish(out.copy(), P2, order, ("u", "v"), ("srx", "sry"), radii, states, left, float(np.float32(c)), k) for c, k in runs]
+
+
+def solve2d1(fields, rx, ry, runs, poi, offset=None, flaw=None):
+    """ICGN2D1::compute(POI2D*) (icgn:144-341) and, with ``offset`` = (ox, oy), ICGN2D1::compute(POI2D*, Point2D&) (icgn:353-547):
+    the same iteration with the local coordinates counted from POI + offset (icgn:400-401, 448-449) and the target subset
+    centred there (icgn:425-426); the reference subset and its gradients stay at the truncated POI (icgn:383-398).
+    Returns (records, one per run; |dp| per iteration)."""
+    out = np.asarray(poi, dtype=np.float64).copy()
+    h, wd = fields.ref.shape
+    if not _guard2d(out, h, wd, rx, ry):
+        out[P2["zncc"]] = -3.0 if out[P2["zncc"]] >= 0 else out[P2["zncc"]]      # icgn:165
+        return [out] * len(runs), []
+    x, y = out[P2["x"]], out[P2["y"]]
+    lx, ly, ref0, ref_norm, (iy, ix) = _subset2d(fields, x, y, rx, ry)
+    ox, oy = (0.0, 0.0) if offset is None else (float(offset[0]), float(offset[1]))
+    fx, fy = lx - ox, ly - oy
+    sd = _sd6(fields.g[0][iy, ix], fields.g[1][iy, ix], fx, fy, rx, flaw)
+    local = np.stack([fx, fy, np.ones_like(fx)])
+    cx, cy = x + ox, y + oy
+
+    def sample(W):
+        q = W @ local                                        # def:94-105, icgn:238-240
+        return bicubic(fields.lut, cx + q[0], cy + q[1])
+
+    wts = _weights(rx, ry, 6, True)
+    p0 = [out[P2[k]] for k in ORDER21]
+    states, left = _iterate(sd, ref0, ref_norm, sample, warp2d1, unwarp2d1, p0, lambda dp: np.sqrt(np.sum(wts * dp * dp)),
+                            0.0, max(k for _, k in runs), flaw)
+    return _records(out, ORDER21, (rx, ry), states, left, runs), [s[1] for s in states]
+
+
+def lm_tie_threshold(samples, znssd, znssd0):
+    """|znssd - znssd0| at or below this is a TIE: float32 cannot be relied on to order the two.  Both are quotients of float32
+    sums of ``samples`` terms accumulated one after the other (the means, the two norms behind the factor |R| / |T|, the squared
+    norm of the error image); such a sum carries a relative error of up to samples * eps (Higham, Accuracy and Stability of
+    Numerical Algorithms, section 4.2), and through the factor |R| / |T| that relative error passes to the ZNSSD once."""
+    return samples * EPS32 * max(znssd, znssd0)
+
+
+def _iterate_lm(sd, ref0, ref_norm, sample, warp, unwarp, p0, conv_norm, stop, damping, flaw, fork=True):
+    """The do ... while of iclm:231-324 / 591-689 with a criterion no iterate reaches: ``stop`` iterations.  Returns the list of
+    PATHS, each a list of states as in _iterate; the first is the model's own.
+
+    Branch ties.  Once converged, successive ZNSSDs differ by less than float32 resolves (lm_tie_threshold), and `znssd <
+    znssd0` is then decided by rounding: on the cases below the model meets such a tie on 2 ... 28 % of the POIs at iteration
+    4 and on 38 ... 100 % at iteration 5, and the compiled reference takes the other branch than the model on up to 16 % of
+    the POIs of a case at k = 5.  Setting those records aside would leave no state after five iterations to compare (and break
+    the 5 % cap on records set aside many times over), so at a tie the model FOLLOWS BOTH BRANCHES (``fork``), and a candidate
+    has to agree with ONE of the paths in every field (select_path).  The tree stays a comb: after a rejection the warp is unchanged, so the next iteration
+    repeats the same comparison on the same two numbers -- in float32 as here -- and rejects again; only the path that accepted
+    can meet a new tie.  At most stop + 1 paths."""
+    lam0, alpha, beta = (float(np.float32(d)) for d in damping)
+    if flaw == "lm_swap":
+        alpha, beta = beta, alpha
+    H = sd.T @ sd                                            # iclm:185-213 / 535-573
+    D = np.diag(np.diag(H)) if flaw == "lm_diag" else np.eye(len(H))
+    paths = []
+    # (warp matrix, p, znssd0, lambda, whether the warp changed since the last comparison, states so far, |dp| of the last
+    # accepted step, the decision forced on the next iteration)
+    pending = [(warp(np.asarray(p0, dtype=np.float64)), np.asarray(p0, dtype=np.float64), 4.0, None, True, [], np.nan, None)]   # iclm:227
+    while pending:
+        W, p, znssd0, lam, fresh, states, norm_kept, forced = pending.pop(0)
+        while len(states) < stop:
+            tar0, tar_norm = _zero_mean(sample(W))           # out-of-range samples enter as -1: no abort (iclm:236-250)
+            with np.errstate(all="ignore"):
+                err = (ref_norm / tar_norm) * tar0 - ref0    # iclm:253
+                znssd = np.sum(err * err) / (ref_norm * ref_norm)    # iclm:256
+                if lam is None:
+                    lam = 0.0 if flaw == "lm_zero" else lam0 ** (znssd / znssd0) - 1.0    # iclm:259-263
+                try:
+                    dp = np.linalg.solve(H + lam * D, sd.T @ err)    # iclm:266-290
+                except np.linalg.LinAlgError:
+                    dp = np.full(len(p), np.nan)
+            accept = bool(fresh and znssd < znssd0)          # iclm:293 (not fresh: the comparison that rejected, repeated)
+            if forced is not None:
+                accept, forced = forced, None
+            elif fork and fresh and abs(znssd - znssd0) <= lm_tie_threshold(len(ref0), znssd, znssd0):
+                pending.append((W, p, znssd0, lam, fresh, list(states), norm_kept, not accept))
+            norm = conv_norm(dp)                             # from the increment, accepted or not (iclm:312-323)
+            if accept:                                       # iclm:293-306
+                lam *= alpha
+                W = W @ np.linalg.inv(warp(dp)) if np.all(np.isfinite(dp)) else np.full(W.shape, np.nan)
+                p = unwarp(W)
+                W = warp(p)
+                if flaw != "lm_keep0":
+                    znssd0 = znssd
+                norm_kept = norm
+            else:                                            # iclm:307-310
+                lam *= beta
+            fresh = accept
+            states.append((p, norm_kept if flaw == "lm_norm_accepted" else norm, znssd))
+        paths.append(states)
+    return paths
+
+
+def solve_lm(fields, dof, rx, ry, runs, poi, damping, flaw=None, fork=True):
+    """ICLM2D1::compute(POI2D*) (iclm:150-358, dof 6) / ICLM2D2::compute(POI2D*) (iclm:502-730, dof 12).  Returns (per run the
+    records of all paths, (paths, 25); per path the |dp| of every iteration); path 0 is the model's own (_iterate_lm)."""
+    out = np.asarray(poi, dtype=np.float64).copy()
+    h, wd = fields.ref.shape
+    if not _guard2d(out, h, wd, rx, ry):
+        out[P2["zncc"]] = -3.0 if out[P2["zncc"]] >= 0 else out[P2["zncc"]]      # iclm:171 / 523
+        return [out[None]] * len(runs), [[]]
+    x, y = out[P2["x"]], out[P2["y"]]
+    lx, ly, ref0, ref_norm, (iy, ix) = _subset2d(fields, x, y, rx, ry)
+    gx, gy = fields.g[0][iy, ix], fields.g[1][iy, ix]
+    if dof == 6:
+        order, warp, unwarp = ORDER21, warp2d1, unwarp2d1
+        sd = _sd6(gx, gy, lx, ly, rx)
+        local, rows = np.stack([lx, ly, np.ones_like(lx)]), (0, 1)
+        p0 = [out[P2[k]] for k in ORDER21]
+    else:
+        order, warp, unwarp = ORDER2, warp2d2, unwarp2d2
+        sd = np.stack([g * f for g in (gx, gy) for f in (1.0, lx, ly, 0.5 * lx * lx, lx * ly, 0.5 * ly * ly)], axis=1)   # iclm:542-562
+        local, rows = np.stack([lx * lx, lx * ly, ly * ly, lx, ly, np.ones_like(lx)]), (3, 4)
+        p0 = [out[P2[k]] if k in ORDER21 else 0.0 for k in ORDER2]               # iclm:579-584: a first-order guess
+
+    def sample(W):
+        q = W @ local
+        return bicubic(fields.lut, x + q[rows[0]], y + q[rows[1]])
+
+    wts = _weights(rx, ry, dof, False)
+    paths = _iterate_lm(sd, ref0, ref_norm, sample, warp, unwarp, p0, lambda dp: np.sqrt(np.sum(wts * dp * dp)),
+                        max(k for _, k in runs), damping, flaw, fork)
+    per_path = [_records(out, order, (rx, ry), states, False, runs) for states in paths]
+    return [np.stack([rp[j] for rp in per_path]) for j in range(len(runs))], [[s[1] for s in states] for states in paths]
+
+
+class FieldsNR:
+    """oracle.PreparedNR2D as float64 data: the reference image and the three tables of the target (nr:119-158)."""
+
+    def __init__(self, prep):
+        self.ref = np.asarray(prep.ref, dtype=np.float64)
+        self.lut, self.lut_gx, self.lut_gy = (np.asarray(a, dtype=np.float64) for a in (prep.lut, prep.lut_gx, prep.lut_gy))
+
+
+def solve_nr(fields, rx, ry, runs, poi, flaw=None):
+    """NR2D1::compute(POI2D*) (nr:160-323): forward-additive.  Every iteration samples the target AND its two gradient tables at
+    the warped positions, builds a new Hessian from them, and ADDS the increment.  Its exits: -1 from the guard (a flag below
+    -1 is kept), then -4 and -5 are tested on whatever the record holds (nr:310-322); subset_radius is not written."""
+    out = np.asarray(poi, dtype=np.float64).copy()
+    h, wd = fields.ref.shape
+    runs = [(float(np.float32(c)), k) for c, k in runs]
+    if not _guard2d(out, h, wd, rx, ry):
+        out[P2["zncc"]] = out[P2["zncc"]] if out[P2["zncc"]] < -1 else -1.0      # nr:170
+        return [_nr_exits(out.copy(), c, k) for c, k in runs], []
+    x, y = out[P2["x"]], out[P2["y"]]
+    lx, ly, ref0, ref_norm, _ = _subset2d(fields, x, y, rx, ry)
+    wts = _weights(rx, ry, 6, True)
+    p = np.array([out[P2[k]] for k in ORDER21])
+    guess = (p[0], p[3])
+    states, H = [], None
+    with np.errstate(all="ignore"):
+        while len(states) < max(k for _, k in runs):
+            qx = x + (1 + p[1]) * lx + p[2] * ly + p[0]      # def:94-105, nr:203-205
+            qy = y + p[4] * lx + (1 + p[5]) * ly + p[3]
+            tar0, tar_norm = _zero_mean(bicubic(fields.lut, qx, qy))             # nr:207, 212
+            if flaw == "nr_grad_at_ref":
+                gx, gy = bicubic(fields.lut_gx, x + lx, y + ly), bicubic(fields.lut_gy, x + lx, y + ly)
+            else:
+                gx, gy = bicubic(fields.lut_gx, qx, qy), bicubic(fields.lut_gy, qx, qy)   # nr:208-209
+            sd = _sd6(gx, gy, lx, ly, rx)                    # nr:225-230
+            if H is None or flaw != "nr_hessian_once":
+                H = sd.T @ sd                                # nr:215-243
+            err = (tar_norm / ref_norm) * ref0 - tar0        # nr:246
+            znssd = np.sum(err * err) / (tar_norm * tar_norm)    # nr:249
+            try:
+                dp = np.linalg.solve(H, sd.T @ err)          # nr:252-273
+            except np.linalg.LinAlgError:
+                dp = np.full(6, np.nan)
+            if flaw == "nr_compose":                         # (an inverse-compositional habit: p o dp instead of p + dp)
+                p = unwarp2d1(warp2d1(p) @ warp2d1(dp))
+            else:
+                p = p + dp                                   # nr:276-277
+            states.append((p, np.sqrt(np.sum(wts * dp * dp)), znssd))            # nr:280-291
+    recs = []
+    for c, stop in runs:
+        n = next(i + 1 for i, s in enumerate(states) if not (i + 1 < stop and s[1] >= c))   # nr:292
+        rec = out.copy()
+        q, norm, znssd = states[n - 1]
+        for k, val in zip(ORDER21, q):                       # nr:295-300
+            rec[P2[k]] = val
+        rec[P2["u0"]], rec[P2["v0"]] = guess                 # nr:303-304
+        rec[P2["zncc"]] = 0.5 * (2.0 - znssd)
+        rec[P2["iteration"]], rec[P2["convergence"]] = n, norm
+        recs.append(_nr_exits(rec, c, stop))
+    return recs, [s[1] for s in states]
+
+
+def _nr_exits(rec, conv, stop):
+    """nr:310-322, run for every record, rejected ones included."""
+    if rec[P2["convergence"]] >= conv and rec[P2["iteration"]] >= stop:
+        rec[P2["zncc"]] = -4.0
+    if np.isnan(rec[P2["zncc"]]) or np.isnan(rec[P2["u"]]) or np.isnan(rec[P2["v"]]):
+        rec[P2["u"]], rec[P2["v"]] = rec[P2["u0"]], rec[P2["v0"]]
+        rec[P2["zncc"]] = -5.0
+    return rec
+
+
+def _runs_of(conv, stop):
+    return [(conv, k) for k in stop] if np.ndim(stop) > 0 else [(conv, stop)]
+
+
+def _queue_runs(res, stop):
+    recs = [np.stack([r[0][j] for r in res]) for j in range(len(res[0][0]))]
+    return (recs if np.ndim(stop) > 0 else recs[0]), [r[1] for r in res]
+
+
+def icgn2d1(fields, rx, ry, conv, stop, pois, offsets=None, flaw=None):
+    """ICGN2D1::compute(poi_queue[, center_offset_queue]), in the calling convention of icgn2d2 above."""
+    return _queue_runs([solve2d1(fields, rx, ry, _runs_of(conv, stop), p, None if offsets is None else offsets[i], flaw)
+                        for i, p in enumerate(pois)], stop)
+
+
+def _own_path(res):
+    return [r[0] for r in res[0]], res[1][0]
+
+
+def iclm2d1(fields, rx, ry, conv, stop, pois, damping, flaw=None):
+    """ICLM2D1::compute(poi_queue): the model's own path (no forks at branch ties)."""
+    return _queue_runs([_own_path(solve_lm(fields, 6, rx, ry, _runs_of(conv, stop), p, damping, flaw, fork=False)) for p in pois], stop)
+
+
+def iclm2d2(fields, rx, ry, conv, stop, pois, damping, flaw=None):
+    return _queue_runs([_own_path(solve_lm(fields, 12, rx, ry, _runs_of(conv, stop), p, damping, flaw, fork=False)) for p in pois], stop)
+
+
+def nr2d1(fields, rx, ry, conv, stop, pois, flaw=None):
+    return _queue_runs([solve_nr(fields, rx, ry, _runs_of(conv, stop), p, flaw) for p in pois], stop)
+
+
 def _queue(res, stop):
     norms = [r[1] for r in res]
     if np.ndim(stop) > 0:
@@ -338,7 +668,8 @@ def trajectory(solver, stop_max=5):
 
 
 def distances(ndim, got, model):
-    """max |got - model| per field group over all POIs (both (n, floats)); ``zncc`` is left to the ordinary run."""
+    """max |got - model| per field group over all POIs (both (n, floats)); ``zncc`` is left to the ordinary run.  ``ndim`` is a
+    key of GROUPS."""
     P = P3 if ndim == 3 else P2
     got = np.asarray(got, dtype=np.float64)
     return {g: float(np.abs(got[:, [P[k] for k in keys]] - model[:, [P[k] for k in keys]]).max())
@@ -443,56 +774,217 @@ def cases2d2():
     return [("2D2", r, ref, tar, prep, fields, pois) for r in [(20, 20), (12, 16)]]
 
 
-def model_runs(case):
-    """(trajectory records for k = 1 ... KMAX, ordinary records, ordinary |dp| lists) of the model on a case."""
-    family, r, _, _, _, fields, pois = case
-    if len(r) == 3:
-        solver = lambda conv, stop: icgn3d1(fields, r[0], r[1], r[2], conv, stop, pois)
-        stop = STOP3
+# The first-order pair of the 6-DoF solvers: a rotation of 2 degrees with 1 % stretch about the image centre, so that ux, vy are
+# near 1e-2 and uy, vx near 3.5e-2 -- a field whose first-order terms matter (at the edge of a 33 x 33 subset they move a sample
+# by half a pixel).  The rotation did not have to come down for the convergence condition (see the header of MEASURED).
+_ROT, _STRETCH = np.deg2rad(2.0), 1.01
+WARP_2D1 = dict(u=1.3, ux=_STRETCH * np.cos(_ROT) - 1.0, uy=-_STRETCH * np.sin(_ROT),
+                v=-0.7, vx=_STRETCH * np.sin(_ROT), vy=_STRETCH * np.cos(_ROT) - 1.0)
+RADII_2D1 = [(16, 16), (7, 9), (36, 36)]      # 1 089 samples: a lone last sample | 285: a partial last pass | 5 329: the fallback shapes
+RADII_LM_NR = [(16, 16), (9, 12)]
+DAMPINGS = [((100.0, 0.1, 10.0), True), ((10.0, 0.5, 4.0), True), ((1000.0, 0.2, 5.0), False)]   # (damping, ordinary run too)
+_PAIR_2D1 = {}
+
+
+def _pair2d1():
+    """(ref, tar, queue of FFTCC2D guesses, its noisy copy, Prepared2D, Fields2D) of the 300 x 320 first-order pair: an 8 x 5
+    grid with a margin of 48 (a 73 x 73 subset and 6 px of displacement fit) plus 10 POIs at non-integer positions."""
+    if not _PAIR_2D1:
+        import oracle
+        from opencorr_amd import synth
+        h, w = 300, 320
+        ref, tar = synth.speckle_pair_2d(h, w, seed=13, warp=WARP_2D1)
+        rng = np.random.default_rng(6403)
+        xs, ys = synth.poi_grid_2d(h, w, 8, 5, 48)
+        xs = np.concatenate([xs, rng.uniform(48, w - 49, 10)]).astype(np.float32)
+        ys = np.concatenate([ys, rng.uniform(48, h - 49, 10)]).astype(np.float32)
+        pois = oracle.make_pois2d(xs, ys)
+        oracle.fftcc2d(ref, tar, 16, 16, pois)
+        noisy = _noisy(pois, P2, 21, rng).astype(np.float32)
+        offsets = rng.uniform(-2.0, 2.0, (20, 2)).astype(np.float32)
+        prep = oracle.Prepared2D(ref, tar)
+        _PAIR_2D1.update(ref=ref, tar=tar, pois=pois, noisy=noisy, offsets=offsets, prep=prep, fields=Fields2D(prep))
+    return _PAIR_2D1
+
+
+def cases2d1():
+    """Family 2D1: ICGN2D1 at RADII_2D1, once on the integer FFTCC2D guesses ("queue": "int") and once on their noisy copy (50
+    records each).  Family 2D1O: compute(poi_queue, center_offset_queue) at (16, 16) on 20 POIs -- 10 of the grid with integer
+    guesses, the 10 off-grid ones noisy -- with offsets within +-2 px."""
+    c = _pair2d1()
+    out = []
+    for r in RADII_2D1:
+        for name in ("pois", "noisy"):
+            out.append(("2D1", r, c["ref"], c["tar"], c["prep"], c["fields"], c[name], dict(solver="icgn2d1", queue=name)))
+    q = np.concatenate([c["pois"][3:40:4], c["noisy"][40:]]).astype(np.float32)
+    out.append(("2D1O", (16, 16), c["ref"], c["tar"], c["prep"], c["fields"], q, dict(solver="icgn2d1", queue="offsets", offsets=c["offsets"])))
+    return out
+
+
+DIM = 1.0 / 64.0
+
+
+def caseslm():
+    """Families LM1 / LM2: ICLM2D1 / ICLM2D2 at RADII_LM_NR.  The default damping on both queues, (10, 0.5, 4) on the noisy one,
+    and (1000, 0.2, 5) on the integer one for the k-iteration states only (it runs into the iteration limit by design).
+
+    Plus one case per family on the DIM pair -- the same two images times 1 / 64 (a power of two: every image-linear float32
+    quantity keeps its bits but for the exponent) -- at (9, 12), default damping, noisy queue.  On 8-bit gray values the Hessian's
+    diagonal is of order 1e5 ... 1e7 and lambda of order 1, so the damping moves no result by more than the bars and a solver
+    without any (flaw "lm_zero") passes every other case here; the ZNSSD, and with it lambda, does not depend on the image's
+    scale, the Hessian does with its square, and on the dim pair the damping decides the third digit of the first step."""
+    c = _pair2d1()
+    if "prep_dim" not in c:
+        import oracle
+        c["ref_dim"], c["tar_dim"] = (c["ref"] * np.float32(DIM)).astype(np.float32), (c["tar"] * np.float32(DIM)).astype(np.float32)
+        c["prep_dim"] = oracle.Prepared2D(c["ref_dim"], c["tar_dim"])
+        c["fields_dim"] = Fields2D(c["prep_dim"])
+    out = []
+    for family, solver in (("LM1", "iclm2d1"), ("LM2", "iclm2d2")):
+        for r in RADII_LM_NR:
+            for (damping, ordinary), names in zip(DAMPINGS, (("pois", "noisy"), ("noisy",), ("pois",))):
+                for name in names:
+                    out.append((family, r, c["ref"], c["tar"], c["prep"], c["fields"], c[name],
+                                dict(solver=solver, queue=name, damping=damping, ordinary=ordinary)))
+        out.append((family, RADII_LM_NR[1], c["ref_dim"], c["tar_dim"], c["prep_dim"], c["fields_dim"], c["noisy"],
+                    dict(solver=solver, queue="noisy", damping=DAMPINGS[0][0], ordinary=True, dim=True)))
+    return out
+
+
+def casesnr():
+    """Family NR1: NR2D1 at RADII_LM_NR on both queues; ``prep`` / ``fields`` hold the target's three tables."""
+    import oracle
+    c = _pair2d1()
+    if "prep_nr" not in c:
+        c["prep_nr"] = oracle.PreparedNR2D(c["ref"], c["tar"])
+        c["fields_nr"] = FieldsNR(c["prep_nr"])
+    return [("NR1", r, c["ref"], c["tar"], c["prep_nr"], c["fields_nr"], c[name], dict(solver="nr2d1", queue=name))
+            for r in RADII_LM_NR for name in ("pois", "noisy")]
+
+
+def cases6dof():
+    return cases2d1() + caseslm() + casesnr()
+
+
+def all_cases():
+    return cases3d() + cases2d2() + cases6dof()
+
+
+def gkey(case):
+    """The key of GROUPS for a case: 3, 2 (12 DoF in 2D) or 21 (6 DoF in 2D)."""
+    return 3 if len(case[1]) == 3 else (2 if case[0] in ("2D2", "LM2") else 21)
+
+
+def _extra(case):
+    """The eighth entry of a case of cases2d1() ... casesnr(); the older cases have seven."""
+    return case[7] if len(case) > 7 else {}
+
+
+def model_runs(case, flaw=None):
+    """(trajectory records for k = 1 ... KMAX, ordinary records, |dp| lists) of the model on a case.  For the IC-LM families the
+    records are (paths, n, floats) and the |dp| lists one per path (_iterate_lm; a POI with fewer paths repeats its path 0).
+    A case that is run for its k-iteration states only ("ordinary": False) has None for the ordinary records.  ``flaw``: the
+    6-DoF solvers with one planted mistake (FLAWS, LM_FLAWS, NR_FLAWS)."""
+    family, r, fields, pois = case[0], case[1], case[5], case[6]
+    extra = _extra(case)
+    solver = extra.get("solver")
+    if solver is None:
+        if len(r) == 3:
+            run = lambda conv, stop: icgn3d1(fields, r[0], r[1], r[2], conv, stop, pois)
+            stop = STOP3
+        else:
+            run = lambda conv, stop: icgn2d2(fields, r[0], r[1], conv, stop, pois)
+            stop = STOP2
+        traj = trajectory(run, KMAX)
+        ordinary, norms = run(CONV, stop)
+        return traj, ordinary, norms
+    ordinary = extra.get("ordinary", True)
+    runs = [(0.0, k) for k in range(1, KMAX + 1)] + ([(CONV, STOP2)] if ordinary else [])    # one sequence of iterations
+    if solver == "icgn2d1":
+        off = extra.get("offsets")
+        res = [solve2d1(fields, r[0], r[1], runs, p, None if off is None else off[i], flaw) for i, p in enumerate(pois)]
+    elif solver in ("iclm2d1", "iclm2d2"):
+        res = [solve_lm(fields, 6 if solver == "iclm2d1" else 12, r[0], r[1], runs, p, extra["damping"], flaw) for p in pois]
     else:
-        solver = lambda conv, stop: icgn2d2(fields, r[0], r[1], conv, stop, pois)
-        stop = STOP2
-    traj = trajectory(solver, KMAX)
-    ordinary, norms = solver(CONV, stop)
-    return traj, ordinary, norms
+        res = [solve_nr(fields, r[0], r[1], runs, p, flaw) for p in pois]
+    if solver.startswith("iclm"):
+        width = max(len(q[1]) for q in res)                  # paths of a POI beyond its own are filled with its path 0
+        recs = [np.stack([np.stack([q[0][j][a if a < len(q[0][j]) else 0] for q in res]) for a in range(width)])
+                for j in range(len(runs))]
+        return recs[:KMAX], recs[KMAX] if ordinary else None, [q[1] + [q[1][0]] * (width - len(q[1])) for q in res]
+    recs = [np.stack([q[0][j] for q in res]) for j in range(len(runs))]
+    return recs[:KMAX], recs[KMAX] if ordinary else None, [q[1] for q in res]
+
+
+def select_path(ndim, radii, got, paths, same_exit=False):
+    """IC-LM: per POI the index of the model's path (_iterate_lm) that ``got`` followed -- the nearest one, all compared fields
+    taken together in pixels at the subset's edge (a gradient times r, a second-order term times r^2 / 2).  ``paths`` is
+    (paths, n, floats).  ``same_exit``: paths with the candidate's flag and iteration count come first."""
+    got = np.asarray(got, dtype=np.float64)
+    r = float(max(radii))
+    scale = {"disp": 1.0, "grad": r, "grad2": 0.5 * r * r, "conv": 1.0}
+    d = np.zeros(paths.shape[:2])
+    for g, keys in GROUPS[ndim].items():
+        if g != "zncc":
+            cols = [P2[k] for k in keys]
+            with np.errstate(invalid="ignore"):
+                d = np.fmax(d, scale[g] * np.abs(paths[:, :, cols] - got[None][:, :, cols]).max(axis=2))
+    if same_exit:
+        flag = lambda a: np.where(a[..., P2["zncc"]] < 0, a[..., P2["zncc"]], 0.0)
+        other = (paths[:, :, P2["iteration"]] != got[None, :, P2["iteration"]]) | (flag(paths) != flag(got)[None])
+        d = d + np.where(other, 1e30, 0.0)
+    return np.nan_to_num(d, nan=1e30).argmin(axis=0)
 
 
 def candidate_runs(case, run):
     """The same runs through ``run(case, conv, stop) -> records`` (the reference build, an oracle order, a GPU engine)."""
     stop = STOP3 if len(case[1]) == 3 else STOP2
-    return [run(case, 0.0, k) for k in range(1, KMAX + 1)], run(case, CONV, stop)
+    return [run(case, 0.0, k) for k in range(1, KMAX + 1)], (run(case, CONV, stop) if _extra(case).get("ordinary", True) else None)
+
+
+REF_ENGINE = {"icgn2d1": 0, "icgn2d2": 1, "iclm2d1": 2, "iclm2d2": 3, "nr2d1": 4}    # oracle.ref.ICGN2D1 ... NR2D1
 
 
 def run_reference(case, conv, stop):
     from oracle import ref as oref
-    family, r, ref, tar, _, _, pois = case
+    r, ref, tar, pois = case[1], case[2], case[3], case[6]
+    extra = _extra(case)
     p = pois.copy()
     if len(r) == 3:
         oref.icgn3d1(ref, tar, r[0], r[1], r[2], conv, stop, p)
     else:
-        oref.solve2d(oref.ICGN2D2, ref, tar, r[0], r[1], conv, stop, p)
+        oref.solve2d(REF_ENGINE[extra.get("solver", "icgn2d2")], ref, tar, r[0], r[1], conv, stop, p,
+                     center_offsets=extra.get("offsets"), damping=extra.get("damping"))
     return p
 
 
 def measure(cases, run, models=None):
     """{family: {group: [k = 1 ... KMAX, ordinary]}} = largest distance of ``run`` from the model over the cases of a family,
-    and {family: (POIs that used the one-iteration exception, POIs)}."""
+    and {family: (POIs that used the one-iteration exception, POIs)}.  Where the model has several paths (IC-LM branch ties),
+    every POI is compared with the path it followed (select_path); no POI is set aside for a tie."""
     dist, exc = {}, {}
     for i, case in enumerate(cases):
-        family, ndim = case[0], len(case[1])
+        family, ndim = case[0], gkey(case)
         traj_m, ord_m, norms = models[i] if models is not None else model_runs(case)
         traj_c, ord_c = candidate_runs(case, run)
         d = dist.setdefault(family, {g: [0.0] * (KMAX + 1) for g in GROUPS[ndim] if g != "zncc"})
         d.setdefault("zncc", [0.0])
+        n = np.arange(len(case[6]))
         for k in range(KMAX):
-            for g, v in distances(ndim, traj_c[k], traj_m[k]).items():
+            mk = traj_m[k] if traj_m[k].ndim == 2 else traj_m[k][select_path(ndim, case[1], traj_c[k], traj_m[k]), n]
+            for g, v in distances(ndim, traj_c[k], mk).items():
                 d[g][k] = max(d[g][k], v)
-        used, dd = compare_ordinary(ndim, family, ord_c, ord_m, norms, CONV)
-        for g, v in dd.items():
-            if g == "zncc":
-                d["zncc"][0] = max(d["zncc"][0], v)
-            else:
-                d[g][ORDINARY] = max(d[g][ORDINARY], v)
+        used = 0
+        if ord_m is not None:
+            if ord_m.ndim == 3:
+                sel = select_path(ndim, case[1], ord_c, ord_m, same_exit=True)
+                ord_m, norms = ord_m[sel, n], [norms[j][a] for j, a in enumerate(sel)]
+            used, dd = compare_ordinary(ndim, family, ord_c, ord_m, norms, CONV)
+            for g, v in dd.items():
+                if g == "zncc":
+                    d["zncc"][0] = max(d["zncc"][0], v)
+                else:
+                    d[g][ORDINARY] = max(d[g][ORDINARY], v)
         a, b = exc.get(family, (0, 0))
         exc[family] = (a + used, b + len(case[6]))
     return dist, exc
@@ -515,9 +1007,10 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     if "--measure" in sys.argv:
         # prints MEASURED / MEASURED_EXCEPTIONS from the compiled reference (paste them at the top of this file)
-        for fam in BARS:   # while measuring, the exception of the ordinary run is judged with the bars being measured
-            BARS[fam]["conv"] = [float("inf")] * (KMAX + 1)
-        dist, exc = measure(cases3d() + cases2d2(), run_reference)
+        cases = all_cases()
+        for fam in set(c[0] for c in cases):   # while measuring, the exception of the ordinary run is judged with the bars being measured
+            BARS.setdefault(fam, {})["conv"] = [float("inf")] * (KMAX + 1)
+        dist, exc = measure(cases, run_reference)
         print("MEASURED = {")
         for fam, groups in dist.items():
             print('    "%s": {%s},' % (fam, ", ".join('"%s": [%s]' % (g, ", ".join("%.3e" % v for v in vals))
