@@ -37,7 +37,9 @@ HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "sift3d_jacobi.h", 
            # the layer table and blur weights of the SIFT3D scale space (host arithmetic only)
            os.path.join("host", "sift3d_plan.h"),
            # the weight tables, the grid of the exact sums and the refusals of its orientation and descriptor stages
-           os.path.join("host", "sift3d_feature_plan.h")]
+           os.path.join("host", "sift3d_feature_plan.h"),
+           # the box-span rule by which ICGN3D1 refuses a volume its 32-bit walk offsets cannot cross
+           os.path.join("host", "volume_limits.h")]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP vectoriser pairs independent scalar fp32 operations into v_pk_mul_f32 / v_pk_add_f32.  On gfx950 a
 # packed op occupies a SIMD for 4.3 cycles against 2.4 for the plain one (profiles/r02b_valu_ubench.json) -- a 10 % gain that the

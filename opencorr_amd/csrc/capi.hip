@@ -6,6 +6,7 @@
 #include "capi_internal.h"
 #include "host/fftcc_plan.h"
 #include "host/icgn2d_plan.h"
+#include "host/volume_limits.h"
 
 namespace ochip_capi {
 
@@ -218,6 +219,17 @@ int check_fftcc2d_limits(const ImagePair& im) {
     if ((unsigned long long)im.dy * (unsigned long long)im.dx > (1ull << 30) || im.dx >= (1 << 24) || im.dy >= (1 << 24))
         return fail(OC_HIP_ERR_UNSUPPORTED, "FFTCC2D: image %d x %d exceeds the engine's limit of %llu pixels (width, height < 2^24)", im.dx,
                     im.dy, 1ull << 30);
+    return OC_HIP_OK;
+}
+
+// ICGN3D1 walks the box of a subvolume with a 32-bit voxel offset (Walk3, icgn3d_device.h): the offset of the box's last sample,
+// 2rz * dy * dx + 2ry * dx + 2rx, must fit 32 bits (host/volume_limits.h).  A volume whose planes are too large for the engine's
+// radii is refused instead of read 2^32 voxels off.  FFTCC3D addresses with size_t: no limit.
+int check_icgn3d_limits(const ImagePair& im, int rx, int ry, int rz) {
+    if (!ochip_host::icgn3d_volume_accepted(rx, ry, rz, im.dy, im.dx))
+        return fail(OC_HIP_ERR_UNSUPPORTED, "ICGN3D1: volume %d x %d x %d with subset radii (%d, %d, %d): the subvolume's box spans %llu voxels of the "
+                                            "volume, beyond the engine's limit of %llu (2 rz * dy * dx + 2 ry * dx + 2 rx < 2^32)",
+                    im.dx, im.dy, im.dz, rx, ry, rz, ochip_host::icgn3d_box_span(rx, ry, rz, im.dy, im.dx), ochip_host::kIcgn3dMaxBoxSpan);
     return OC_HIP_OK;
 }
 
@@ -503,6 +515,7 @@ int run_icgn3d1(oc_hip_engine* e, float* d_pois, int stride_f, size_t count) {
     if (!e->ref_ready || !e->tar_ready)
         return fail(OC_HIP_ERR_INVALID, "ICGN3D1: prepare() has not been called since the last set_images");
     const ImagePair& im = *e->img;
+    OC_TRY(check_icgn3d_limits(im, e->rx, e->ry, e->rz));   // (the radii may have changed since prepare(): set_subset)
     int blocks = 0;
     size_t scratch = ochip::icgn3d1_scratch_floats(e->rx, e->ry, e->rz, &blocks);
     // the one-pass arithmetic contract (icgn3d_onepass.hip) stores no sample: no scratch.  It has one mapping; a call that asks for
@@ -1023,6 +1036,7 @@ int oc_hip_prepare_ref(oc_hip_engine* e) {
         OC_TRY(e->gy.reserve(bytes));
         OC_HIP_TRY(ochip::launch_grad2d(im.ref_ptr(), im.dy, im.dx, e->gx.as<float>(), e->gy.as<float>(), e->stream));
     } else {
+        OC_TRY(check_icgn3d_limits(im, e->rx, e->ry, e->rz));   // (before any buffer is reserved)
         OC_TRY(e->gx.reserve(bytes));
         OC_TRY(e->gy.reserve(bytes));
         OC_TRY(e->gz.reserve(bytes));
@@ -1066,6 +1080,7 @@ int oc_hip_prepare_tar(oc_hip_engine* e) {
             OC_HIP_TRY(ochip::launch_bspline2d_lut(e->gy.as<float>(), im.dy, im.dx, e->coef_gy.as<float>(), e->stream));
         }
     } else {
+        OC_TRY(check_icgn3d_limits(im, e->rx, e->ry, e->rz));   // (before any buffer is reserved)
         OC_TRY(e->coef.reserve(im.count() * sizeof(float)));
         // the y pass needs a second volume.  It stays with the engine (grow-only, like every other buffer): allocating and
         // freeing 537 MB around every prepare() of a 512^3 volume cost ~1 ms of hipMalloc / hipFree plus a stream drain --
@@ -1107,6 +1122,7 @@ static int compute_impl(oc_hip_engine* e, void* pois, const float* offsets, size
     // (FFTCC2D's image limit is known before anything moves: refused before a host queue is staged or an event recorded;
     // run_fftcc2d asks again for the paths that do not come through here)
     if (e->kind == OC_HIP_FFTCC2D && e->img && e->img->ndim == 2) OC_TRY(check_fftcc2d_limits(*e->img));
+    if (e->kind == OC_HIP_ICGN3D1 && e->img && e->img->ndim == 3) OC_TRY(check_icgn3d_limits(*e->img, e->rx, e->ry, e->rz));   // (likewise)
     TailGuard tail(e);  // also the error exits leave the enqueued work covered by the tail event
     // a queue of a few POIs is not worth waking the other devices for; "group_force_rccl" sends a lone engine's DEVICE
     // queue down the group path as well (a group of one, whose all-gather is a one-rank ncclAllGather)

@@ -307,8 +307,10 @@ __device__ __forceinline__ float bspline3d_eval_lds(const float* __restrict__ wi
 struct Walk3 {
     int i, j, k, s;
     int SX, SY, di, dj, dk;
+    // 32-bit and UNSIGNED throughout: a box may span up to 2^32 - 1 voxels (host/volume_limits.h; larger ones are refused), so
+    // the products pass 2^31 and the increments are taken modulo 2^32 -- defined for unsigned, undefined for int
     unsigned off;
-    int doff, coff_k, coff_j;
+    unsigned doff, coff_k, coff_j;
     __device__ __forceinline__ Walk3(int tid, int SX_, int SY_, int first_pass = 0, int DX = 0, int DY = 0)
         : SX(SX_), SY(SY_) {
         // The walk's start state depends on the thread index and the subset shape only, so the optimiser computes ALL the
@@ -326,10 +328,11 @@ struct Walk3 {
         rem = kBlock3d - di * plane;
         dj = rem / SX_;
         dk = rem - dj * SX_;
-        off = (unsigned)((i * DY + j) * DX + k);
-        doff = (di * DY + dj) * DX + dk;
-        coff_k = DX - SX_;          // k wrapped: one row further, SX columns back
-        coff_j = (DY - SY_) * DX;   // j wrapped: one plane further, SY rows back
+        const unsigned UX = (unsigned)DX, UY = (unsigned)DY;
+        off = ((unsigned)i * UY + (unsigned)j) * UX + (unsigned)k;
+        doff = ((unsigned)di * UY + (unsigned)dj) * UX + (unsigned)dk;
+        coff_k = UX - (unsigned)SX_;          // k wrapped: one row further, SX columns back
+        coff_j = (UY - (unsigned)SY_) * UX;   // j wrapped: one plane further, SY rows back
     }
     __device__ __forceinline__ void next() {
         s += kBlock3d;
@@ -337,11 +340,11 @@ struct Walk3 {
         off += doff;
         const bool ck = k >= SX;
         k = ck ? k - SX : k;
-        off += ck ? coff_k : 0;
+        off += ck ? coff_k : 0u;
         j += dj + (ck ? 1 : 0);
         const bool cj = j >= SY;
         j = cj ? j - SY : j;
-        off += cj ? coff_j : 0;
+        off += cj ? coff_j : 0u;
         i += di + (cj ? 1 : 0);
     }
 };

@@ -51,9 +51,10 @@ struct RowWalk {
         j = row - i * SY_;
         di = kHalves / SY_;
         dj = kHalves - di * SY_;
-        off = (unsigned)((i * DY + j) * DX);
-        doff = (unsigned)((di * DY + dj) * DX);
-        coff = (unsigned)((DY - SY_) * DX);  // j wrapped: one plane further, SY rows back
+        const unsigned UX = (unsigned)DX, UY = (unsigned)DY;  // (unsigned products: see Walk3)
+        off = ((unsigned)i * UY + (unsigned)j) * UX;
+        doff = ((unsigned)di * UY + (unsigned)dj) * UX;
+        coff = (UY - (unsigned)SY_) * UX;  // j wrapped: one plane further, SY rows back
     }
     __device__ __forceinline__ void next() {
         row += kHalves;
