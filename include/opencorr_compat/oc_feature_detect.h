@@ -13,8 +13,14 @@
 //
 // Differences a caller can observe ("SIFT3D scale space" and "SIFT3D orientation and descriptors"): where a blur
 // radius exceeds dim - 1 on an axis the reference's mirrored index leaves the array, here it is clamped into the axis; sums over
-// a keypoint's window are exact instead of sequential float32; the eigen-decomposition is a Jacobi iteration in double.  SIFT2D
-// and FeatureAffine are not part of this header.
+// a keypoint's window are exact instead of sequential float32; the eigen-decomposition is a Jacobi iteration in double.
+//
+//   SIFT2DScaleSpace   the detector of SIFT2D::compute (src/oc_sift.cpp:60-93): setSiftConfig with the reference's Sift2dConfig;
+//                      compute(Image2D*) builds the Gaussian and DoG pyramids of cv::SIFT::detect on the device;
+//                      detect(kp_queue) appends the located keypoints (position, size, response, octave, layer) in the scan order
+//                      of the extrema they started from.  Orientation, descriptors, duplicate removal, n_features trimming and
+//                      SIFT2D::compute itself are not part of this header yet ("SIFT2D detector"); FeatureAffine
+//                      lives in oc_feature_affine.h.
 #pragma once
 
 #include <cstdlib>
@@ -293,6 +299,92 @@ private:
     SIFT3DScaleSpace extractor_[2];  // one per image: each keeps its descriptor block alive until the match is done
     DescriptorMatcher3D matcher_;
     bool bidirectional_ = false;
+};
+
+// src/oc_sift.h:30-37
+struct Sift2dConfig {
+    int n_features;
+    int n_octave_layers;
+    float contrast_threshold;
+    float edge_threshold;
+    float sigma;
+};
+
+// one located keypoint of cv::SIFT::detect before orientation: the members of cv::KeyPoint that are final at that point, and the
+// cell and offsets the next stages read
+struct Keypoint2D {
+    Point2D pt;
+    float size, response;
+    int octave, layer;   // octave as cv::SIFT counts it (-1 = the doubled base)
+    int row, col;
+    float offset_col, offset_row, offset_layer;
+    int packed_octave;   // cv::KeyPoint::octave
+};
+
+class SIFT2DScaleSpace {
+public:
+    SIFT2DScaleSpace() {
+        // SIFT2D::SIFT2D(), src/oc_sift.cpp:22-30
+        sift_config.n_features = 0;
+        sift_config.n_octave_layers = 3;
+        sift_config.contrast_threshold = 0.04f;
+        sift_config.edge_threshold = 10.f;
+        sift_config.sigma = 1.6f;
+        hipdetail::check(oc_hip_sift2d_create(hipdetail::default_device(), &engine_));
+    }
+    ~SIFT2DScaleSpace() { (void)oc_hip_destroy(engine_); }
+    SIFT2DScaleSpace(const SIFT2DScaleSpace&) = delete;
+    SIFT2DScaleSpace& operator=(const SIFT2DScaleSpace&) = delete;
+
+    Sift2dConfig getSiftConfig() const { return sift_config; }
+    void setSiftConfig(Sift2dConfig config) { sift_config = config; }  // src/oc_sift.cpp:44-47
+
+    // the pyramids of cv::SIFT::detect (:86) of img; they stay on the device
+    void compute(Image2D* img) {
+        hipdetail::check(oc_hip_sift2d_set_config(engine_, sift_config.n_features, sift_config.n_octave_layers, sift_config.contrast_threshold,
+                                                  sift_config.edge_threshold, sift_config.sigma));
+        std::vector<float> rows((size_t)img->width * img->height);
+        for (int r = 0; r < img->height; r++)
+            for (int c = 0; c < img->width; c++) rows[(size_t)r * img->width + c] = img->eg_mat(r, c);
+        hipdetail::check(oc_hip_sift2d_set_image(engine_, rows.data(), 1, img->width, img->height, OC_HIP_HOST));
+        hipdetail::check(oc_hip_sift2d_build(engine_));
+    }
+
+    int getOctaveNumber() const {
+        int n_layers = 0, n_octave = 0;
+        hipdetail::check(oc_hip_sift2d_layer_count(engine_, 0, &n_layers, &n_octave));
+        return n_octave;
+    }
+
+    // the located keypoints (:86), appended to kp_queue
+    void detect(std::vector<Keypoint2D>& kp_queue) {
+        size_t n = 0;
+        hipdetail::check(oc_hip_sift2d_keypoint_count(engine_, &n));
+        std::vector<oc_hip_sift2d_keypoint> list(n);
+        if (n > 0) hipdetail::check(oc_hip_sift2d_detect(engine_, list.data(), n, &n, OC_HIP_HOST));
+        for (size_t i = 0; i < n; i++) {
+            Keypoint2D kp{};
+            kp.pt.x = list[i].x;
+            kp.pt.y = list[i].y;
+            kp.size = list[i].size;
+            kp.response = list[i].response;
+            kp.octave = list[i].octave;
+            kp.layer = list[i].layer;
+            kp.row = list[i].row;
+            kp.col = list[i].col;
+            kp.offset_col = list[i].xc;
+            kp.offset_row = list[i].xr;
+            kp.offset_layer = list[i].xi;
+            kp.packed_octave = list[i].packed_octave;
+            kp_queue.push_back(kp);
+        }
+    }
+
+    oc_hip_engine* engine() const { return engine_; }
+
+private:
+    Sift2dConfig sift_config;
+    oc_hip_engine* engine_ = nullptr;
 };
 
 }  // namespace opencorr

@@ -87,7 +87,8 @@ typedef enum oc_hip_kind {
     OC_HIP_STEREOVISION = 12,
     OC_HIP_MATCHER = 13,
     OC_HIP_SIFT3D = 14,
-    OC_HIP_FEATURE_AFFINE = 15
+    OC_HIP_FEATURE_AFFINE = 15,
+    OC_HIP_SIFT2D = 16
 } oc_hip_kind;
 
 #define OC_HIP_POI2D_BYTES 100
@@ -633,6 +634,53 @@ int oc_hip_sift3d_orient(oc_hip_engine* engine, const oc_hip_sift3d_candidate* c
  * million keypoints are 3 GB. */
 int oc_hip_sift3d_describe(oc_hip_engine* engine, const oc_hip_sift3d_keypoint* keypoints, size_t n, int keypoints_memory,
                            float* descriptors, int memory);
+
+/* ---- SIFT2D's detector: scale space and located keypoints ------------------ */
+/* The front half of SIFT2D::compute() (src/oc_sift.cpp:60-93): what cv::SIFT::detect does before it assigns orientations, for
+ * the cv::SIFT that SIFT2D creates (:65-79) from its Sift2dConfig (:22-30) -- the 2x upscaled base image, the Gaussian and DoG
+ * pyramids, the 26-neighbour extrema scan and the sub-pixel localisation with its contrast and edge rejections.  The
+ * arithmetic contract is DESIGN.md section 4.13: float32, every multiply and add rounding on its own ("arith_fma" is refused:
+ * this engine has one arithmetic).  The output is the list of located keypoints in the scan order of the extremum each one
+ * started from (octave, layer, row, column), the same from run to run; two starts that end in one cell both stay.  Orientation,
+ * descriptors, duplicate removal, n_features trimming and matching are not part of this engine.  Refused before anything is
+ * launched: image sides below 2, n_octave_layers outside [1, 8], a sigma that is not finite or not > 0 (OC_HIP_ERR_INVALID);
+ * a doubled base image above 2^31-1 pixels, a blur radius above 32 or below 1 (a
+ * blur sigma below 0.0625), n_features != 0 (OC_HIP_ERR_UNSUPPORTED); oc_hip_sift2d_build
+ * refuses an image with a non-finite pixel (OC_HIP_ERR_INVALID).  The handle takes oc_hip_set_stream, oc_hip_set_tuning (the keys
+ * every kind accepts) and oc_hip_destroy; oc_hip_compute*, oc_hip_set_images* and oc_hip_set_devices are refused
+ * (OC_HIP_ERR_UNSUPPORTED).  Settings at creation: those of SIFT2D::SIFT2D() (:22-30). */
+typedef struct oc_hip_sift2d_keypoint {   /* 48 bytes */
+    float x, y;             /* cv::KeyPoint::pt in pixels of the input image */
+    float size, response;   /* cv::KeyPoint::size, ::response */
+    int octave, layer;      /* octave as cv::SIFT counts it (-1 = the doubled base), layer 1 ... n_octave_layers */
+    int row, col;           /* the cell of that octave the localisation ended in */
+    float xc, xr, xi;       /* its offsets from the cell: column, row, layer */
+    int packed_octave;      /* cv::KeyPoint::octave */
+} oc_hip_sift2d_keypoint;
+/* SIFT2D::SIFT2D() (src/oc_sift.cpp:22-30) */
+int oc_hip_sift2d_create(int device, oc_hip_engine** out);
+/* the members of Sift2dConfig (src/oc_sift.h:30-37); SIFT2D::setSiftConfig (src/oc_sift.cpp:44-47), cv::SIFT::create (:65-70) */
+int oc_hip_sift2d_set_config(oc_hip_engine* engine, int n_features, int n_octave_layers, float contrast_threshold, float edge_threshold,
+                             float sigma);
+/* the image cv::SIFT::detect is given (:86): [row][col], pixel_type 0 = uint8, 1 = float32 on the 0 ... 255 scale; a HOST image
+ * is copied, a DEVICE image (4-byte aligned when float32) is used in place and must stay valid until oc_hip_sift2d_build has returned */
+int oc_hip_sift2d_set_image(oc_hip_engine* engine, const void* data, int pixel_type, int width, int height, int memory);
+/* the pyramids of cv::SIFT::detect (:86); they stay on the device */
+int oc_hip_sift2d_build(oc_hip_engine* engine);
+/* pyramid 0 = Gaussian, 1 = DoG (:86) */
+int oc_hip_sift2d_layer_count(const oc_hip_engine* engine, int pyramid, int* n_layers, int* n_octave);
+/* dims = { cols, rows }; octave counts from 0 at the doubled base; sigma and radius of the blur that made a Gaussian layer (0 for
+ * a resampled one and for DoG layers); threshold: the integer the extrema scan compares fabsf(v) with (:86) */
+int oc_hip_sift2d_layer_info(const oc_hip_engine* engine, int pyramid, int index, int* dims, int* octave, float* sigma, int* radius,
+                             int* threshold);
+/* one layer, cols x rows float32, where `memory` says (:86) */
+int oc_hip_sift2d_get_layer(oc_hip_engine* engine, int pyramid, int index, float* out, int memory);
+/* the number of located keypoints of the pyramid as built (:86); the detection runs once per build */
+int oc_hip_sift2d_keypoint_count(oc_hip_engine* engine, size_t* n);
+/* The located keypoints (:86) where `memory` says, at most `capacity` records; *n (required) receives their number.  capacity
+ * smaller than that: OC_HIP_ERR_INVALID, nothing is written and *n carries the needed size.  The list also stays in the engine.
+ * The call waits for the stream. */
+int oc_hip_sift2d_detect(oc_hip_engine* engine, oc_hip_sift2d_keypoint* out, size_t capacity, size_t* n, int memory);
 
 /* ---- FeatureAffine2D / FeatureAffine3D: the keypoint-guided affine initial guess ---- */
 /* src/oc_feature_affine.{h,cpp}: per POI the matched keypoints inside the search radius (the neighbor_number_min nearest when

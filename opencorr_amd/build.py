@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libopencorr_hip.so")
-SOURCES = ["capi.hip", "capi_host.hip", "capi_group.hip", "capi_strain.hip", "capi_stereo.hip", "capi_match.hip", "match.hip", "capi_sift3d.hip", "capi_feature_affine.hip", "feature_affine.hip", "sift3d.hip", "sift3d_features.hip", "stereo.hip", "prepare2d.hip", "icgn2d.hip", "icgn2d_onepass.hip", "nr2d.hip", "poi_order.hip", "poi_split.hip", "strain.hip", "fftcc2d.hip", "fftcc2d_fused.hip", "fftcc2d_fusedn.hip", "fftcc2d_fusedp.hip", "fftcc2d_fusedr.hip", "fftcc2d_rect.hip", "prepare3d.hip", "icgn3d.hip", "icgn3d_onepass.hip", "fftcc3d.hip", "fftcc3d_fused.hip", "fftcc3d_fusedn.hip", "fftcc3d_box.hip", "fftcc3d_planes.hip", "fftcc3d_planesb.hip"]
+SOURCES = ["capi.hip", "capi_host.hip", "capi_group.hip", "capi_strain.hip", "capi_stereo.hip", "capi_match.hip", "match.hip", "capi_sift3d.hip", "capi_sift2d.hip", "capi_feature_affine.hip", "feature_affine.hip", "sift3d.hip", "sift3d_features.hip", "sift2d.hip", "stereo.hip", "prepare2d.hip", "icgn2d.hip", "icgn2d_onepass.hip", "nr2d.hip", "poi_order.hip", "poi_split.hip", "strain.hip", "fftcc2d.hip", "fftcc2d_fused.hip", "fftcc2d_fusedn.hip", "fftcc2d_fusedp.hip", "fftcc2d_fusedr.hip", "fftcc2d_rect.hip", "prepare3d.hip", "icgn3d.hip", "icgn3d_onepass.hip", "fftcc3d.hip", "fftcc3d_fused.hip", "fftcc3d_fusedn.hip", "fftcc3d_box.hip", "fftcc3d_planes.hip", "fftcc3d_planesb.hip"]
 # the A/B build: sources that exist only there, and the product sources whose code depends on OC_BUILD_AB (recompiled with
 # -DOC_BUILD_AB=1; every other object is shared with the product build)
 AB_ONLY_SOURCES = ["icgn3d_rows.hip", "icgn2d_band.hip", "fftcc3d_fused_r5.hip"]
@@ -38,6 +38,9 @@ HEADERS = ["capi_internal.h", "oc_device.h", "oc_kernels.h", "sift3d_jacobi.h", 
            os.path.join("host", "sift3d_plan.h"),
            # the weight tables, the grid of the exact sums and the refusals of its orientation and descriptor stages
            os.path.join("host", "sift3d_feature_plan.h"),
+           # the octave count, layer table, blur weights, threshold and refusals of the SIFT2D detector (sift2d.hip reads its
+           # 2^t and its constants: KERNEL_SOURCES names it)
+           os.path.join("host", "sift2d_plan.h"),
            # the box-span rule by which ICGN3D1 refuses a volume its 32-bit walk offsets cannot cross
            os.path.join("host", "volume_limits.h")]
 ARCH = "gfx950"
@@ -69,6 +72,7 @@ KERNEL_SOURCES = {
     "sift_blur": ["sift3d.hip", "oc_device.h"],
     "sift_orient_kernel": ["sift3d_features.hip", "sift3d_jacobi.h", "oc_device.h"],
     "sift_describe_kernel": ["sift3d_features.hip", "sift3d_jacobi.h", "oc_device.h"],
+    "sift2d_": ["sift2d.hip", "oc_device.h", os.path.join("host", "sift2d_plan.h")],
     "feature_affine_kernel": ["feature_affine.hip", "oc_device.h"],
     "fftcc3d_planes_kernel": ["fftcc3d_planes_impl.h", "fftcc3d_planes.hip", "fftcc3d_planesb.hip", "fft_device.h", "oc_device.h", os.path.join("host", "fftcc_plan.h")],
 }

@@ -18,7 +18,7 @@ ERR_INVALID, ERR_HIP, ERR_ROCFFT, ERR_NOMEM, ERR_UNSUPPORTED = 1, 2, 3, 4, 5
 HOST, DEVICE = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 FFTCC2D, ICGN2D1, ICGN2D2, FFTCC3D, ICGN3D1, NR2D1, ICLM2D1, ICLM2D2, STRAIN, REGION_FIT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
-CALIBRATION, STEREOVISION, MATCHER, SIFT3D, FEATURE_AFFINE = 11, 12, 13, 14, 15
+CALIBRATION, STEREOVISION, MATCHER, SIFT3D, FEATURE_AFFINE, SIFT2D = 11, 12, 13, 14, 15, 16
 POI2D_BYTES, POI3D_BYTES, POI2DS_BYTES = 100, 124, 112
 POI2D_FLOATS, POI3D_FLOATS, POI2DS_FLOATS = 25, 31, 28
 POI2DS = 22  # the `ndim` of oc_hip_strain_prepare / oc_hip_strain_compute that selects POI2DS records
@@ -49,6 +49,8 @@ SYMBOLS = [
     "oc_hip_sift3d_create", "oc_hip_sift3d_set_config", "oc_hip_sift3d_set_physical_unit", "oc_hip_sift3d_set_volume", "oc_hip_sift3d_build",
     "oc_hip_sift3d_layer_count", "oc_hip_sift3d_layer_info", "oc_hip_sift3d_get_layer", "oc_hip_sift3d_detect",
     "oc_hip_sift3d_candidate_count", "oc_hip_sift3d_set_feature_config", "oc_hip_sift3d_orient", "oc_hip_sift3d_describe",
+    "oc_hip_sift2d_create", "oc_hip_sift2d_set_config", "oc_hip_sift2d_set_image", "oc_hip_sift2d_build", "oc_hip_sift2d_layer_count",
+    "oc_hip_sift2d_layer_info", "oc_hip_sift2d_get_layer", "oc_hip_sift2d_keypoint_count", "oc_hip_sift2d_detect",
     "oc_hip_feature_affine_create", "oc_hip_feature_affine_set_search", "oc_hip_feature_affine_set_ransac", "oc_hip_feature_affine_set_seed",
     "oc_hip_feature_affine_set_self_adaptive", "oc_hip_feature_affine_set_keypoints", "oc_hip_feature_affine_set_matched",
     "oc_hip_feature_affine_prepare", "oc_hip_feature_affine_compute",
@@ -211,6 +213,15 @@ def lib():
     L.oc_hip_sift3d_set_feature_config.argtypes = [vp, f, f, f, f]
     L.oc_hip_sift3d_orient.argtypes = [vp, vp, sz, i, vp, sz, psz, vp, vp, i]
     L.oc_hip_sift3d_describe.argtypes = [vp, vp, sz, i, vp, i]
+    L.oc_hip_sift2d_create.argtypes = [i, pp]
+    L.oc_hip_sift2d_set_config.argtypes = [vp, i, i, f, f, f]
+    L.oc_hip_sift2d_set_image.argtypes = [vp, vp, i, i, i, i]
+    L.oc_hip_sift2d_build.argtypes = [vp]
+    L.oc_hip_sift2d_layer_count.argtypes = [vp, i, vp, vp]
+    L.oc_hip_sift2d_layer_info.argtypes = [vp, i, i, vp, vp, vp, vp, vp]
+    L.oc_hip_sift2d_get_layer.argtypes = [vp, i, i, vp, i]
+    L.oc_hip_sift2d_keypoint_count.argtypes = [vp, psz]
+    L.oc_hip_sift2d_detect.argtypes = [vp, vp, sz, psz, i]
     L.oc_hip_feature_affine_create.argtypes = [i, i, i, i, i, pp]
     L.oc_hip_feature_affine_set_search.argtypes = [vp, f, i]
     L.oc_hip_feature_affine_set_ransac.argtypes = [vp, i, i, f]

@@ -709,6 +709,7 @@ int oc_hip_set_images2d(oc_hip_engine* e, const float* ref, const float* tar, in
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: the SIFT3D scale space takes one volume (oc_hip_sift3d_set_volume)");
+    if (e->is_sift2d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: the SIFT2D detector takes one image (oc_hip_sift2d_set_image)");
     if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images2d: a FeatureAffine engine holds no images (oc_hip_feature_affine_set_keypoints)");
     if (e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images2d called on a 3D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null image pointer");
@@ -751,6 +752,7 @@ int oc_hip_set_images3d(oc_hip_engine* e, const float* ref, const float* tar, in
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: a descriptor matcher holds no images (oc_hip_matcher_set_descriptors)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: the SIFT3D scale space takes one volume (oc_hip_sift3d_set_volume)");
+    if (e->is_sift2d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: the SIFT2D detector takes one image (oc_hip_sift2d_set_image)");
     if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_images3d: a FeatureAffine engine holds no images (oc_hip_feature_affine_set_keypoints)");
     if (!e->is3d()) return fail(OC_HIP_ERR_INVALID, "set_images3d called on a 2D engine");
     if (!ref || !tar) return fail(OC_HIP_ERR_INVALID, "null volume pointer");
@@ -841,6 +843,7 @@ int oc_hip_set_devices(oc_hip_engine* e, const int* device_ids, int n_devices) {
     if (n_devices > 1 && (e->kind == OC_HIP_STRAIN || e->kind == OC_HIP_REGION_FIT))
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: Strain / RegionFit need every neighbour of a POI and stay on one device");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a SIFT3D scale space stays on the device it was created for");
+    if (e->is_sift2d()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a SIFT2D detector stays on the device it was created for");
     if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a FeatureAffine engine needs every keypoint around a POI and has no device groups");
     if (n_devices > 1 && e->is_matcher())
         return fail(OC_HIP_ERR_UNSUPPORTED, "set_devices: a descriptor matcher needs every candidate of a query and stays on one device");
@@ -1110,6 +1113,7 @@ static int compute_impl(oc_hip_engine* e, void* pois, const float* offsets, size
     OC_ACTIVATE(e);
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT3D scale space has no POI queue (oc_hip_sift3d_build / oc_hip_sift3d_detect)");
+    if (e->is_sift2d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT2D detector has no POI queue (oc_hip_sift2d_build / oc_hip_sift2d_detect)");
     if (e->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a FeatureAffine engine computes through oc_hip_feature_affine_compute");
     if (count == 0) return OC_HIP_OK;
     if (!pois) return fail(OC_HIP_ERR_INVALID, "null POI buffer");
@@ -1162,6 +1166,8 @@ int oc_hip_compute_chain(oc_hip_engine* const* engines, int n_engines, void* poi
         if (engines[i]->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: a descriptor matcher has no POI queue");
     for (int i = 0; i < n_engines; i++)
         if (engines[i]->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: the SIFT3D scale space has no POI queue");
+    for (int i = 0; i < n_engines; i++)
+        if (engines[i]->is_sift2d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: the SIFT2D detector has no POI queue");
     for (int i = 0; i < n_engines; i++)
         if (engines[i]->is_feature_affine()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute_chain: a FeatureAffine engine computes through oc_hip_feature_affine_compute, before the chain");
     if (n_engines == 1) return compute_impl(engines[0], pois, nullptr, count, stride_bytes, memory);
@@ -1288,6 +1294,7 @@ static void serve_single_batch(oc_hip_engine* e, std::vector<oc_hip_engine::Sing
 static int compute_single(oc_hip_engine* e, void* poi, const float* offset) {
     if (e->is_matcher()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: a descriptor matcher has no POI queue (oc_hip_matcher_nearest / oc_hip_matcher_match)");
     if (e->is_sift3d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT3D scale space has no POI queue (oc_hip_sift3d_build / oc_hip_sift3d_detect)");
+    if (e->is_sift2d()) return fail(OC_HIP_ERR_UNSUPPORTED, "compute: the SIFT2D detector has no POI queue (oc_hip_sift2d_build / oc_hip_sift2d_detect)");
     if (!poi) return fail(OC_HIP_ERR_INVALID, "null POI");
     if (!e->single_combine) return compute_impl(e, poi, offset, 1, e->poi_bytes(), OC_HIP_HOST);
     oc_hip_engine::SingleCombiner::Request req(poi, offset);

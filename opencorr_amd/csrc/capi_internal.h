@@ -56,6 +56,7 @@ ncclResult_t ncclGetVersion(int* version);
 #include "host/engine_tuning.h"
 #include "host/sift3d_plan.h"
 #include "host/sift3d_feature_plan.h"
+#include "host/sift2d_plan.h"
 #include "host/single_combiner.h"
 
 namespace ochip_capi {
@@ -279,6 +280,16 @@ struct DeviceState {
     bool sf_oriented = false;  // sf_kp holds sf_kp_count keypoints of the pyramid as built
     size_t sf_kp_count = 0;
     size_t sf_desc_floats = 0;  // what the last describe(descriptors = NULL, OC_HIP_DEVICE) left in sf_desc ("descriptors" of oc_hip_get_field)
+    // SIFT2D detector (capi_sift2d.hip): the image (a HOST image is copied into s2_img, a DEVICE one is used in place), both pyramids
+    // resident for the later stages, ONE scratch image of base size (the rows pass of every blur; the upscaled input before the
+    // first one lies in s2_base), the table of DoG layers the localisation reads, the scan scratch, the starts, their verdicts
+    // and records, the list of located keypoints
+    const void* s2_ext = nullptr;
+    DevBuf s2_img, s2_base, s2_scratch, s2_table, s2_flag, s2_scan, s2_starts, s2_status, s2_slots, s2_kscan, s2_kp;
+    std::vector<DevBuf> s2_gauss, s2_dog;
+    bool s2_built = false;
+    bool s2_detected = false;  // s2_kp holds the s2_kp_count keypoints of the pyramid as built
+    size_t s2_kp_count = 0;
     // FFTCC working set
     FftPlans fft;
     DevBuf win, freq, norms, flags;
@@ -340,6 +351,12 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
     ochip_host::Sift3dFeatureSettings sf_fcfg;
     float sf_vol_max = 0.f;
     ochip_host::Sift3dFeaturePlan sf_fplan;
+    // SIFT2D detector (capi_sift2d.hip; cv::SIFT as SIFT2D::compute() creates it, src/oc_sift.cpp:22-30, 60-93): the settings, the
+    // image's sides and pixel type, the plan of the last build (host/sift2d_plan.h)
+    ochip_host::Sift2dSettings s2_cfg;
+    int s2_width = 0, s2_height = 0;
+    bool s2_u8 = false;
+    ochip_host::Sift2dPlan s2_plan;
     ochip_host::ChunkHandoff chunk_handoff;  // the copy-out thread sleeps here until the next chunk has been handed over
     std::atomic<unsigned> single_calls{0};  // compute(POI*) calls on this engine (one hint on stderr when a caller loops over them)
     // Combining front end of compute(POI*) (host/single_combiner.h): callers that arrive while a launch is in flight are queued;
@@ -366,6 +383,7 @@ struct oc_hip_engine : ochip_host::EngineTuning, DeviceState {
 
     bool is_matcher() const { return kind == OC_HIP_MATCHER; }
     bool is_sift3d() const { return kind == OC_HIP_SIFT3D; }
+    bool is_sift2d() const { return kind == OC_HIP_SIFT2D; }
     bool is_feature_affine() const { return kind == OC_HIP_FEATURE_AFFINE; }
     bool is3d() const { return kind == OC_HIP_FFTCC3D || kind == OC_HIP_ICGN3D1; }
     bool is_iclm() const { return kind == OC_HIP_ICLM2D1 || kind == OC_HIP_ICLM2D2; }

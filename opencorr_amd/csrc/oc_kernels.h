@@ -499,4 +499,53 @@ hipError_t launch_sift_orient_fill(const int* status, const SiftKeypoint* slots,
 // constructDescriptor for n validated keypoints: out[768 i ...]
 hipError_t launch_sift_describe(const SiftKeypoint* list, size_t n, const SiftFeatureParams& p, float* out, hipStream_t stream);
 
+// ---- sift2d.hip -------------------------------------------------------------
+// SIFT2D's detector: cv::SIFT as SIFT2D::compute() creates it (src/oc_sift.cpp:22-30, 60-93), the contract of DESIGN.md section
+// 4.13.  Images are [row][col] float32.  Per blurred pixel and pass: acc = w[0] * s[c], then r = 1 ... radius ascending
+// acc = acc + w[r] * (s[lo] + s[hi]), every operation rounding on its own, lo / hi by reflect-101 repeated until inside.
+constexpr int kSift2dMaxRadius = 32;
+// dst (2 cols x 2 rows) = the bilinear 2x upscale of src (uint8 when src_u8, else float32); *flag (set to 0 before) is raised by a
+// non-finite source pixel
+hipError_t launch_sift2d_upscale(const void* src, bool src_u8, int cols, int rows, float* dst, unsigned* flag, hipStream_t stream);
+// rows pass: dst = src blurred along x
+hipError_t launch_sift2d_blur_rows(const float* src, float* dst, int cols, int rows, const SiftWeights& w, int radius, hipStream_t stream);
+// columns pass: dst = src blurred along y; with dog: dog = dst - prev at every pixel (prev: the Gaussian layer the blur started from)
+hipError_t launch_sift2d_blur_cols(const float* src, float* dst, int cols, int rows, const SiftWeights& w, int radius, const float* prev, float* dog,
+                                   hipStream_t stream);
+// nearest-neighbour resample: dst[y][x] = src[min(floor(y * (double)src_rows / dst_rows), src_rows - 1)][the same in x]
+hipError_t launch_sift2d_resample(const float* src, int src_cols, int src_rows, float* dst, int dst_cols, int dst_rows, hipStream_t stream);
+// One DoG layer of the extrema scan: rows and columns in [5, size - 5); a pixel is a candidate when fabsf(v) > threshold and
+// v > 0 and v >= all 26 neighbours, or v < 0 and v <= all 26.  A workgroup owns kSiftExtremaVoxels consecutive pixels;
+// first_block: its workgroups' place among those of all scanned layers, in list order.
+struct Sift2dExtremaLayer {
+    const float *below, *here, *above;
+    int cols, rows, octave, layer;   // octave counts from 0 at the doubled base
+    float threshold;
+    unsigned first_block;
+};
+struct Sift2dStart {
+    int octave, layer, row, col;
+};
+hipError_t launch_sift2d_extrema_count(const Sift2dExtremaLayer& layer, unsigned* block_counts, hipStream_t stream);
+hipError_t launch_sift2d_extrema_fill(const Sift2dExtremaLayer& layer, const unsigned* block_offsets, Sift2dStart* out, hipStream_t stream);
+struct Sift2dDogLayer {   // device table, n_octave * (n_octave_layers + 2)
+    const float* data;
+    int cols, rows;
+};
+struct Sift2dKeypoint {   // oc_hip_sift2d_keypoint
+    float x, y, size, response;
+    int octave, layer, row, col;
+    float xc, xr, xi;
+    int packed_octave;
+};
+struct Sift2dLocalizeParams {
+    const Sift2dDogLayer* dog;
+    int n_octave, n_octave_layers;
+    float contrast_threshold, edge_threshold, sigma;
+};
+// one thread per start: status[i] = 0 and slots[i] = the record when start i is located, status[i] != 0 when it is rejected
+hipError_t launch_sift2d_localize(const Sift2dStart* starts, size_t n, const Sift2dLocalizeParams& p, int* status, Sift2dKeypoint* slots, hipStream_t stream);
+// the located slots in start order: launch_sift_orient_count -> launch_block_count_scan -> this
+hipError_t launch_sift2d_fill(const int* status, const Sift2dKeypoint* slots, size_t n, const unsigned* block_offsets, Sift2dKeypoint* out, hipStream_t stream);
+
 }  // namespace ochip

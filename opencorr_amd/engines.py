@@ -973,6 +973,109 @@ class SIFT3DScaleSpace(_Handle):
         return out
 
 
+class SIFT2DScaleSpace(_Handle):
+    """SIFT2DScaleSpace() -- the detector of SIFT2D::compute (src/oc_sift.cpp:60-93): what cv::SIFT::detect does before it assigns
+    orientations, for the cv::SIFT that SIFT2D creates from its Sift2dConfig (:22-30).  The 2x upscaled base, the Gaussian and DoG
+    pyramids (``build``), and the located keypoints after the 26-neighbour extrema scan and the sub-pixel localisation with its
+    contrast and edge rejections (``detect``), in the scan order of the extremum each one started from.  Images are (rows, cols)
+    uint8 or float32 on the 0 ... 255 scale; a NumPy image is copied, a CUDA torch tensor is used in place by ``build``.  Both
+    pyramids and the list stay on the device.  Orientation, descriptors, duplicate removal, ``n_features`` trimming and matching
+    are not part of this engine."""
+
+    KEYPOINT = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("response", np.float32),
+                         ("octave", np.int32), ("layer", np.int32), ("row", np.int32), ("col", np.int32),
+                         ("xc", np.float32), ("xr", np.float32), ("xi", np.float32), ("packed_octave", np.int32)])
+    LAYER = np.dtype([("dims", np.int32, 2), ("octave", np.int32), ("sigma", np.float32), ("radius", np.int32), ("threshold", np.int32)])
+    GAUSSIAN, DOG = 0, 1
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        self._image = None
+        capi.check(capi.lib().oc_hip_sift2d_create(int(device), ctypes.byref(self._h)))
+
+    def set_tuning(self, key, value):
+        """The keys every engine kind accepts; this engine has one arithmetic (``"arith_fma"`` = 1 is refused)."""
+        capi.check(capi.lib().oc_hip_set_tuning(self._h, key.encode(), int(value)))
+
+    def set_config(self, n_features=0, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6):
+        """The members of Sift2dConfig; the defaults are SIFT2D::SIFT2D()'s (src/oc_sift.cpp:22-30).  ``n_features`` must be 0."""
+        capi.check(capi.lib().oc_hip_sift2d_set_config(self._h, int(n_features), int(n_octave_layers), float(contrast_threshold),
+                                                       float(edge_threshold), float(sigma)))
+
+    def set_image(self, image):
+        """``image``: (rows, cols) uint8 or float32, a NumPy array or a contiguous CUDA torch tensor."""
+        if len(image.shape) != 2:
+            raise ValueError("the image must have shape (rows, cols)")
+        rows, cols = (int(v) for v in image.shape)
+        if _is_torch(image):
+            import torch
+            if image.dtype not in (torch.uint8, torch.float32) or not image.is_contiguous() or not image.is_cuda:
+                raise ValueError("a torch image must be a contiguous CUDA tensor of uint8 or float32 (pass NumPy arrays for host data)")
+            self._adopt_stream_of(image)
+            ptr, mem, keep, u8 = ctypes.c_void_p(image.data_ptr()), capi.DEVICE, image, image.dtype == torch.uint8
+        else:
+            u8 = np.asarray(image).dtype == np.uint8
+            keep = np.ascontiguousarray(image, dtype=np.uint8 if u8 else np.float32)
+            ptr, mem = ctypes.c_void_p(keep.ctypes.data), capi.HOST
+        capi.check(capi.lib().oc_hip_sift2d_set_image(self._h, ptr, 0 if u8 else 1, cols, rows, mem))
+        self._image = keep if mem == capi.DEVICE else None   # a device image is used in place: keep it alive
+
+    def build(self):
+        """The Gaussian and DoG pyramids of cv::SIFT::detect (src/oc_sift.cpp:86)."""
+        capi.check(capi.lib().oc_hip_sift2d_build(self._h))
+
+    def layers(self, pyramid):
+        """One ``LAYER`` record per layer of the Gaussian (0) or DoG (1) pyramid; dims are (cols, rows)."""
+        n, n_oct = ctypes.c_int(), ctypes.c_int()
+        capi.check(capi.lib().oc_hip_sift2d_layer_count(self._h, int(pyramid), ctypes.byref(n), ctypes.byref(n_oct)))
+        out = np.zeros(n.value, dtype=self.LAYER)
+        for i in range(n.value):
+            dims = (ctypes.c_int * 2)()
+            octave, sigma, radius, threshold = ctypes.c_int(), ctypes.c_float(), ctypes.c_int(), ctypes.c_int()
+            capi.check(capi.lib().oc_hip_sift2d_layer_info(self._h, int(pyramid), i, dims, ctypes.byref(octave), ctypes.byref(sigma),
+                                                           ctypes.byref(radius), ctypes.byref(threshold)))
+            out[i] = (tuple(dims), octave.value, sigma.value, radius.value, threshold.value)
+        return out
+
+    def layer(self, pyramid, index, out=None):
+        """One layer as a (rows, cols) float32 array; ``out``: a CUDA torch tensor of that shape to fill instead."""
+        dims = (ctypes.c_int * 2)()
+        capi.check(capi.lib().oc_hip_sift2d_layer_info(self._h, int(pyramid), int(index), dims, None, None, None, None))
+        shape = (dims[1], dims[0])
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        elif tuple(out.shape) != shape:
+            raise ValueError("layer: the output must have shape %r" % (shape,))
+        if _is_torch(out):
+            ptr, mem, _ = _buf(out)
+        else:
+            if out.dtype != np.float32 or not out.flags.c_contiguous:
+                raise ValueError("layer: the output must be a contiguous float32 array")
+            ptr, mem = ctypes.c_void_p(out.ctypes.data), capi.HOST
+        capi.check(capi.lib().oc_hip_sift2d_get_layer(self._h, int(pyramid), int(index), ptr, mem))
+        return out
+
+    def keypoint_count(self):
+        n = ctypes.c_size_t()
+        capi.check(capi.lib().oc_hip_sift2d_keypoint_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def detect(self, on_device=False):
+        """The located keypoints: a ``KEYPOINT`` array, or with ``on_device`` a CUDA int32 tensor (n, 12) of the records' words."""
+        n = self.keypoint_count()
+        got = ctypes.c_size_t()
+        if on_device:
+            import torch
+            out = torch.empty((n, self.KEYPOINT.itemsize // 4), dtype=torch.int32, device="cuda:%d" % self._device)
+            if n:
+                capi.check(capi.lib().oc_hip_sift2d_detect(self._h, ctypes.c_void_p(out.data_ptr()), n, ctypes.byref(got), capi.DEVICE))
+            return out
+        out = np.empty(n, dtype=self.KEYPOINT)
+        if n:
+            capi.check(capi.lib().oc_hip_sift2d_detect(self._h, ctypes.c_void_p(out.ctypes.data), n, ctypes.byref(got), capi.HOST))
+        return out
+
+
 class SIFT3D:
     """SIFT3D() -- SIFT3D::compute (src/oc_sift.cpp:234-293) end to end on the GPU: two extractions (``SIFT3DScaleSpace``: pyramids,
     extrema, orientation, descriptors) and the brute-force matching of ``DescriptorMatcher``; descriptors go from one to the other
